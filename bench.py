@@ -13,6 +13,11 @@ with 0.1% nulls, seed 42, synthetic (no network). Total work is FIXED as N
 grows (scaling: strong).
 
 Run:  python bench.py [--gpus N] [--steps K] [--warmup W] [--rows R]
+                      [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times the K steps and prints the result line.
+--dump-outputs DIR also writes the final aggregate of the LAST timed step as
+DIR/<name>.npy; --full adds the CPU baseline leg (`cpu_baseline`, null in a
+plain run).
 N>1 is launched by the driver via torch.distributed.run (one rank per GPU,
 RCCL backend); rank/world read from the env.
 """
@@ -207,11 +212,51 @@ def run_step(ba, plan, dev_input, world, rank, torch, dist, device, stats):
     tm = mark("s3_final", tm)
     nfinal = t2.metric("num_groups")
     stats["num_groups"] = nfinal
+    # the step's result: the final task's output batches (host numpy columns
+    # key / sum / cnt, copied out by import_batch during t2.run())
+    stats["last_outputs"] = t2.outputs
     t2.finalize()
     if world == 1:
         keep[0].free()
     del keep
     return nfinal
+
+
+DUMP_NAMES = ("key", "sum", "cnt")
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, batches, rank, world):
+    """Write the final aggregate the last timed step returned (what a caller
+    of run_step's final task receives, in the engine's own row order) as
+    float64 DIR/<name>.npy plus a float32 0/1 DIR/<name>_valid.npy per
+    column; null slots are written as 0. int64 keys/counts here are < 2^53,
+    so float64 holds them exactly (asserted). Past 64 MB in all, a fixed
+    seeded row sample (sorted indices, row order kept) is written instead."""
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    cols = []
+    for i, name in enumerate(DUMP_NAMES):
+        vals = np.concatenate([ob[i]["values"] for ob in batches]) \
+            if batches else np.empty(0, np.float64)
+        valid = np.concatenate([
+            ob[i]["valid"] if ob[i]["valid"] is not None
+            else np.ones(len(ob[i]["values"]), bool) for ob in batches]) \
+            if batches else np.empty(0, bool)
+        if vals.dtype.kind == "i":
+            assert (np.abs(vals[valid]) < (1 << 53)).all(), \
+                f"{name}: int64 value not exact in float64"
+        vals = np.where(valid, vals, 0).astype(np.float64)
+        cols.append((name, vals, valid.astype(np.float32)))
+    n = len(cols[0][1])
+    row_bytes = len(cols) * (8 + 4)
+    if n * row_bytes > DUMP_MAX_BYTES:
+        keep = np.sort(np.random.default_rng(SEED).choice(
+            n, DUMP_MAX_BYTES // row_bytes, replace=False))
+        cols = [(nm, v[keep], m[keep]) for nm, v, m in cols]
+    for name, vals, valid in cols:
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), vals)
+        np.save(os.path.join(out_dir, f"{name}_valid{suffix}.npy"), valid)
 
 
 def cpu_baseline_leg(total_rows):
@@ -319,7 +364,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--rows", type=int, default=TOTAL_ROWS_DEFAULT,
                     help="TOTAL rows across all ranks (strong scaling)")
-    ap.add_argument("--skip-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's final aggregate as "
+                         "DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the CPU baseline leg (cpu_baseline)")
+    ap.add_argument("--skip-cpu-baseline", action="store_true",
+                    help="with --full: leave the CPU baseline leg out")
     args = ap.parse_args()
 
     import torch
@@ -376,6 +427,10 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, stats.get("last_outputs") or [],
+                     rank, world)
+
     if rank == 0:
         print(f"[bench] stage seconds over {args.steps} steps: "
               f"{stats.get('stage_s', {})}", file=sys.stderr, flush=True)
@@ -391,8 +446,8 @@ def main():
             "frac": round(achieved_gbs / 8000.0, 4),
             "traffic": None,  # PMC traffic in profiles/ (rocprofv3), see DESIGN.md
         }
-        cpu = None if args.skip_cpu_baseline or world > 1 else \
-            cpu_baseline_leg(args.rows)
+        cpu = cpu_baseline_leg(args.rows) if args.full and world == 1 \
+            and not args.skip_cpu_baseline else None
         out = {
             "metric": METRIC,
             "value": round(value, 1),
