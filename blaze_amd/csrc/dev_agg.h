@@ -1,8 +1,8 @@
 // dev_agg.h — shared device-side helpers for the aggregation kernels:
 // murmur3 restatement (mur.rs:19-87), slot-table probe, typed accumulate,
 // the a8 Binary agg-buf freeze/parse wire logic (acc.rs / count.rs /
-// first.rs / collect.rs formats). Inline-only; included by kernels.hip and
-// kernels_gkey.hip so the WIRE logic has exactly one definition.
+// first.rs / collect.rs formats). Inline-only; included by every
+// aggregation .hip file so each helper has exactly one definition.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -206,9 +206,9 @@ __device__ __forceinline__ int varint_len_dev(uint64_t v) {
   return k;
 }
 
-// agg layout: 3 bits per agg, LSB-first, 0-terminated. All aggs share one
-// argument column, so SUM/AVG parts duplicate the same sum and COUNT/AVG
-// parts the same count (avg.rs:208-217: AVG freeze = sum ++ count).
+// agg layout: one 4-bit nibble per agg, LSB-first, 0-terminated. All aggs
+// share one argument column, so SUM/AVG parts duplicate the same sum and
+// COUNT/AVG parts the same count (avg.rs:208-217: AVG freeze = sum ++ count).
 // AGGL_SUM=1, AGGL_CNT=2, AGGL_AVG=3, AGGL_MIN=4, AGGL_MAX=5; MIN/MAX parts
 // are prim freezes [u8 valid][8B LE f64]? like SUM's (acc.rs:335-347 — the
 // maxmin accumulator is the same generic prim column, maxmin.rs:91-93).

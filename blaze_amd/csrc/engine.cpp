@@ -583,16 +583,6 @@ class AggOp {
   }
 
   ~AggOp() {
-    if (s_aux_) {
-      (void)hipStreamSynchronize(s_aux_);
-      (void)hipStreamDestroy(s_aux_);
-      for (int i = 0; i < 2; i++) {
-        (void)hipEventDestroy(ev_scatter_[i]);
-        (void)hipEventDestroy(ev_merge_[i]);
-        (void)hipEventDestroy(ev_read_[i]);
-      }
-      (void)hipEventDestroy(ev_pipe_[0]);
-    }
     for (auto& [e0, e1] : ev_pairs_) {
       (void)hipEventDestroy(e0);
       (void)hipEventDestroy(e1);
@@ -717,14 +707,6 @@ class AggOp {
       // holds {key,cnt,sum,first} only (perf note in DESIGN.md)
       if (!gkey_ && !ma_mode_ && !merge_mode_ && !has_mm_ && !has_first_ &&
           !has_coll_ && b.num_rows - done >= AGG2_MIN_CHUNK) {
-        init_agg2_conf();
-        if (agg2_v3_ && agg2_pipe_ && !skip_enabled_ &&
-            b.num_rows - done >= 2 * agg2_chunk_max_) {
-          // multi-chunk batch: cross-chunk pipeline — scatter(k+1) on the
-          // aux stream overlaps bucket/merge(k) on the engine stream
-          done = two_phase_pipelined(b, done);
-          continue;
-        }
         int64_t chunk2 = std::min(b.num_rows - done, agg2_chunk_max_);
         if (done + chunk2 < b.num_rows) chunk2 &= ~(int64_t)7;
         two_phase_chunk(b, done, chunk2);
@@ -1369,8 +1351,9 @@ class AggOp {
                              stream_));
     AURON_HIP(hipStreamSynchronize(stream_));
     if (*err) {
-      // bit 1: table probe exhausted; 16: gkey pool publish spin; 32: v3
-      // scatter tile bound; 64: v4 scatter ring-space retry bound
+      // bit 1: table probe exhausted; 16: gkey pool publish spin; 32:
+      // scatter tile bound; 64: reserved (was the removed ring scatter's
+      // retry bound) — do not reuse
       if (*err & ~1u)
         FAIL("agg device error flags 0x" +
              ([](uint32_t v) {
@@ -1475,10 +1458,12 @@ class AggOp {
   // tails and per-chunk syncs (24 B/row + 24 B/row leftover scratch; 256M
   // rows = 12 GB of the 288 GB HBM). Runtime-tunable for A/B sweeps.
   int64_t agg2_chunk_max_ = 256 << 20;
-  static constexpr int AGG2_NBUCK_LOG2 = 10;
-  static constexpr int AGG3_NBUCK_LOG2 = 9;   // v3: 512 buckets
+  static constexpr int AGG3_NBUCK_LOG2 = 9;   // 512 buckets
   static constexpr int AGG3_NBUCK = 1 << AGG3_NBUCK_LOG2;
-  static constexpr int AGG3_GRID_LOG2 = 8;    // v3 scatter: 256 x 1024-thr           // 1024 buckets: scatter write-line footprint ~L2-sized (512 buckets overflow the 2048-slot LDS window: 2.3% leftovers, 3x slower)
+  static constexpr int AGG3_GRID_LOG2 = 8;    // hist/scatter grid: 256 blocks
+                                              // x 1024 threads
+  // staged-group capacity: every bucket's full 4096-slot LDS window
+  static constexpr int64_t AGG3_STAGED_CAP = (int64_t)AGG3_NBUCK * 4096;
 
   // ---- multi-argument chunk (kernels_maarg.hip) --------------------------
   void ma_chunk(const DevBatch& b, int64_t done, int64_t chunk) {
@@ -1668,378 +1653,123 @@ class AggOp {
   void init_agg2_conf() {
     if (agg2_conf_read_) return;
     agg2_conf_read_ = true;
-    // A/B toggle for the partition-record layout: the 24B AoS record
-    // (default) vs 16B kv + 4B rowv split streams — measured a wash within
-    // box noise; AURON_AGG2_SPLIT=1 selects the split for experiments.
-    const char* e = getenv("AURON_AGG2_SPLIT");
-    agg2_split_ = (e && e[0] == '1');
-    // hist/scatter grid (blocks = 1<<log2): 512 default (same-box sweeps:
-    // occupancy beats write locality — grid 256/128 measured slower)
-    const char* g = getenv("AURON_AGG2_GRID_LOG2");
-    if (g && g[0]) agg2_grid_log2_ = atoi(g);
-    if (agg2_grid_log2_ < 6 || agg2_grid_log2_ > AGG2_GRID_LOG2_MAX)
-      agg2_grid_log2_ = 9;
-    // hist/scatter/bucket workgroup size: 1024 threads = 16 waves/block
-    // fill the chip's 32-wave/CU slots (the 256-thread launch left the
-    // bucket kernel at 12 waves/CU = 38% occupancy; microarch guide
-    // "Chip-level parameters"/"Register files")
-    const char* bl = getenv("AURON_AGG2_BLOCK");
-    if (bl && bl[0]) agg2_block_ = atoi(bl);
-    if (agg2_block_ != 256 && agg2_block_ != 512 && agg2_block_ != 1024)
-      agg2_block_ = 1024;
     const char* cm = getenv("AURON_AGG2_CHUNK_M");  // millions of rows
     if (cm && cm[0]) {
       int64_t m = atoll(cm);
       if (m >= 4 && m <= 1024) agg2_chunk_max_ = m << 20;
     }
-    // v3 pipeline (default): LDS-staged packet scatter, 512 buckets,
-    // 4096-slot bucket window — kernels_agg3.hip header comment has the
-    // evidence trail. AURON_AGG2_V3=0 falls back to the v2 kernels.
-    const char* v3 = getenv("AURON_AGG2_V3");
-    agg2_v3_ = !(v3 && v3[0] == '0');
-    // cross-chunk pipeline: OFF by default — the scatter (151 KB LDS/WG)
-    // and bucket (100 KB) kernels cannot co-reside on a CU, so overlapping
-    // them only splits the chip and adds sync bubbles (measured 60.5 vs
-    // 51 ms/step); kept behind AURON_AGG2_PIPE=1 for experiments
-    const char* pe = getenv("AURON_AGG2_PIPE");
-    agg2_pipe_ = (pe && pe[0] == '1');
-    // v4 scatter: barrier-free producer/flusher rings (kernels_agg3.hip) —
-    // experimental until measured; AURON_AGG2_V4=1 selects it
-    const char* v4 = getenv("AURON_AGG2_V4");
-    agg2_v4_ = (v4 && v4[0] == '1');
     const char* p16 = getenv("AURON_AGG2_P16");
     agg2_p16_en_ = !(p16 && p16[0] == '0');
   }
 
-  // Cross-chunk pipelined two-phase aggregation (v3 kernels): the scatter
-  // chain of chunk k+1 runs on the aux stream while the bucket/merge of
-  // chunk k runs on the engine stream. Per-chunk scratch is
-  // double-buffered; the counter readback of chunk k completes while
-  // scatter(k+1) is in flight, so the host enqueues merges without stalling
-  // the device. MERGES ENQUEUE BEFORE THE NEXT BUCKET so the shared staged
-  // list is consumed in engine-stream order. Partial skipping is disabled
-  // on this path (checked by the caller).
-  int64_t two_phase_pipelined(const DevBatch& b, int64_t done) {
-    const DevColumn& keyc = b.cols.at(key_col_);
-    const DevColumn& valc = b.cols.at(val_col_);
-    init_pipeline_scratch();
-    struct Chunk {
-      int64_t beg = 0, n = 0;
-      uint64_t row0 = 0;
-    };
-    std::vector<Chunk> chunks;
-    int64_t total = b.num_rows;
-    uint64_t rc = row_cursor_;
-    while (done < total && total - done >= AGG2_MIN_CHUNK) {
-      Chunk c;
-      c.beg = done;
-      c.n = std::min(total - done, agg2_chunk_max_);
-      if (done + c.n < total) c.n &= ~(int64_t)7;
-      c.row0 = rc;
-      chunks.push_back(c);
-      done += c.n;
-      rc += (uint64_t)c.n;
-    }
-    hipEvent_t e0, e1;
-    AURON_HIP(hipEventCreate(&e0));
-    AURON_HIP(hipEventCreate(&e1));
-    AURON_HIP(hipEventRecord(e0, stream_));
-    // the aux stream must not run ahead of prior work on the engine stream
-    AURON_HIP(hipEventRecord(ev_pipe_[0], stream_));
-    AURON_HIP(hipStreamWaitEvent(s_aux_, ev_pipe_[0], 0));
-    const int nbuck = AGG3_NBUCK;
-    int64_t mat3 = (int64_t)nbuck << AGG3_GRID_LOG2;
-    for (size_t k = 0; k <= chunks.size(); k++) {
-      if (k < chunks.size()) {
-        // aux stream: hist -> line scan -> scatter for chunk k
-        const Chunk& c = chunks[k];
-        int pb = (int)(k & 1);
-        const int64_t* keys = (const int64_t*)keyc.values + c.beg;
-        const double* vals = (const double*)valc.values + c.beg;
-        const uint8_t* kv =
-            keyc.validity ? keyc.validity + c.beg / 8 : nullptr;
-        const uint8_t* vv =
-            valc.validity ? valc.validity + c.beg / 8 : nullptr;
-        // partbuf/leftover[pb] are free once chunk k-2's MERGES completed
-        // (the merge event implies its bucket read finished too)
-        if (k >= 2)
-          AURON_HIP(hipStreamWaitEvent(s_aux_, ev_merge_[pb], 0));
-        AURON_HIP(hipMemsetAsync(d_pctr_[pb].get(), 0, 24, s_aux_));
-        launch_agg2_hist(keys, kv, c.n, AGG3_NBUCK_LOG2, AGG3_GRID_LOG2,
-                         d_pcounts_[pb].get<uint32_t>(),
-                         (uint32_t*)(d_pctr_[pb].get<uint8_t>() + 16), 1024,
-                         s_aux_);
-        launch_agg3_line_sizes(d_pcounts_[pb].get<uint32_t>(), mat3 + 1,
-                               d_plinesz_[pb].get<uint32_t>(), 24, s_aux_);
-        size_t tb = d_pscan_tmp_.size();
-        scan_counts_matrix(d_plinesz_[pb].get<uint32_t>(),
-                           d_pscanned_[pb].get<uint32_t>(), mat3 + 1,
-                           d_pscan_tmp_.get(), &tb, s_aux_);
-        launch_agg3_scatter(keys, kv, vals, vv, c.n, AGG3_NBUCK_LOG2,
-                            AGG3_GRID_LOG2, d_pscanned_[pb].get<uint32_t>(),
-                            d_ppart_[pb].get<uint8_t>(),
-                            d_pleft_[pb].get<PartRow>(),
-                            d_pctr_[pb].get<unsigned long long>() + 1,
-                            d_plinesz_[pb].get<uint32_t>(),
-                            t_.error_flag, 24, 0, s_aux_);
-        AURON_HIP(hipEventRecord(ev_scatter_[pb], s_aux_));
-      }
-      if (k > 0) {
-        // merges for chunk k-1; the readback completes while scatter(k)
-        // runs on the aux stream
-        const Chunk& c = chunks[k - 1];
-        int pb = (int)((k - 1) & 1);
-        AURON_HIP(hipEventSynchronize(ev_read_[pb]));
-        unsigned long long* h = pin_pctr_[pb].get<unsigned long long>();
-        int64_t staged_n = (int64_t)h[0];
-        int64_t lo_n = (int64_t)h[1];
-        uint32_t special_rows = (uint32_t)h[2];
-        ng_true_ = h[4];
-        ng_bound_ = ng_true_ + (special_rows ? 2u : 0u);
-        if (special_rows) {
-          const int64_t* keys = (const int64_t*)keyc.values + c.beg;
-          const double* vals = (const double*)valc.values + c.beg;
-          const uint8_t* kv =
-              keyc.validity ? keyc.validity + c.beg / 8 : nullptr;
-          const uint8_t* vv =
-              valc.validity ? valc.validity + c.beg / 8 : nullptr;
-          launch_agg2_specials(t_, keys, kv, vals, vv, c.n, c.row0, stream_);
+  // Merge a COUNTED list of n table inserts (staged groups or leftover
+  // rows) piecewise, so a VRAM budget (spill) smaller than the list still
+  // works; launch(done, piece) enqueues entries [done, done+piece).
+  template <class Launch>
+  void merge_counted(int64_t n, Launch launch) {
+    for (int64_t done2 = 0; done2 < n;) {
+      ensure_capacity((int64_t)ng_bound_ +
+                      std::min<int64_t>(n - done2, 1 << 20));
+      int64_t free2 = t_.cap * 3 / 4 - (int64_t)ng_bound_;
+      if (free2 < (1 << 14)) {
+        refresh_ng();
+        free2 = t_.cap * 3 / 4 - (int64_t)ng_true_;
+        if (free2 < (1 << 14)) {
+          spill_table();
+          continue;
         }
-        // capacity: exact counted bounds; growth forces a full pipeline sync
-        if (t_.cap * 3 / 4 < (int64_t)ng_bound_ + staged_n + lo_n) {
-          AURON_HIP(hipStreamSynchronize(s_aux_));
-          ensure_capacity((int64_t)ng_bound_ + staged_n + lo_n);
-        }
-        launch_agg2_merge_groups(t_, d_staged_.get<StagedGroup>(), staged_n,
-                                 c.row0, stream_);
-        if (lo_n)
-          launch_agg2_leftovers(t_, d_pleft_[pb].get<PartRow>(), lo_n,
-                                c.row0, stream_);
-        AURON_HIP(hipEventRecord(ev_merge_[pb], stream_));
-        ng_bound_ += (uint64_t)(staged_n + lo_n);
-        update_rows_ += c.n;
-        row_cursor_ += (uint64_t)c.n;
       }
-      if (k < chunks.size()) {
-        // engine stream: bucket(k) after scatter(k); stream order places it
-        // after merge(k-1) as well
-        int pb = (int)(k & 1);
-        AURON_HIP(hipStreamWaitEvent(stream_, ev_scatter_[pb], 0));
-        launch_agg3_bucket(d_ppart_[pb].get<uint8_t>(),
-                           d_pcounts_[pb].get<uint32_t>(),
-                           d_plinesz_[pb].get<uint32_t>(),
-                           d_pscanned_[pb].get<uint32_t>(), AGG3_GRID_LOG2,
-                           val_is_int_ ? 1 : 0, nbuck,
-                           d_staged_.get<StagedGroup>(),
-                           d_pctr_[pb].get<unsigned long long>(),
-                           (int64_t)nbuck * 4096, d_pleft_[pb].get<PartRow>(),
-                           d_pctr_[pb].get<unsigned long long>() + 1,
-                           t_.error_flag, 24, 0, stream_);
-        AURON_HIP(hipMemcpyAsync(pin_pctr_[pb].get(), d_pctr_[pb].get(), 24,
-                                 hipMemcpyDeviceToHost, stream_));
-        AURON_HIP(hipMemcpyAsync(pin_pctr_[pb].get<uint8_t>() + 32,
-                                 t_.num_groups, 8, hipMemcpyDeviceToHost,
-                                 stream_));
-        AURON_HIP(hipEventRecord(ev_read_[pb], stream_));
-      }
+      int64_t piece = std::min(n - done2, free2);
+      launch(done2, piece);
+      done2 += piece;
+      ng_bound_ += (uint64_t)piece;
     }
-    AURON_HIP(hipEventRecord(e1, stream_));
-    ev_pairs_.push_back({e0, e1});
-    return chunks.empty() ? done : chunks.back().beg + chunks.back().n;
-  }
-
-  void init_pipeline_scratch() {
-    if (d_ppart_[0]) return;
-    init_agg2_conf();
-    const int nbuck = AGG3_NBUCK;
-    int64_t mat3 = (int64_t)nbuck << AGG3_GRID_LOG2;
-    int64_t part_bytes =
-        agg2_chunk_max_ * 24 + ((int64_t)nbuck << AGG3_GRID_LOG2) * 64;
-    for (int i = 0; i < 2; i++) {
-      d_ppart_[i].alloc(part_bytes);
-      d_pleft_[i].alloc(agg2_chunk_max_ * sizeof(PartRow));
-      d_pcounts_[i].alloc((mat3 + 1) * 4);
-      d_plinesz_[i].alloc((mat3 + 1) * 4);
-      d_pscanned_[i].alloc((mat3 + 1) * 4);
-      d_pctr_[i].alloc(24);
-      pin_pctr_[i].alloc(64);
-      AURON_HIP(hipEventCreate(&ev_scatter_[i]));
-      AURON_HIP(hipEventCreate(&ev_merge_[i]));
-      AURON_HIP(hipEventCreate(&ev_read_[i]));
-    }
-    AURON_HIP(hipEventCreate(&ev_pipe_[0]));
-    size_t tb = 0;
-    scan_counts_matrix(d_plinesz_[0].get<uint32_t>(),
-                       d_pscanned_[0].get<uint32_t>(), mat3 + 1, nullptr,
-                       &tb, stream_);
-    d_pscan_tmp_.alloc(tb);
-    if (!d_staged_)
-      d_staged_.alloc((int64_t)nbuck * 4096 * sizeof(StagedGroup));
-    if (!d_leftover_) d_leftover_.alloc(agg2_chunk_max_ * sizeof(PartRow));
-    AURON_HIP(hipStreamCreateWithFlags(&s_aux_, hipStreamNonBlocking));
   }
 
   // Two-phase aggregation of rows [done, done+chunk) of batch b:
-  // histogram -> scatter to bucket-major SoA -> per-bucket LDS aggregate ->
-  // merge counted staged groups into the slot table (kernels_agg2.hip).
+  // histogram -> line-padded scan -> LDS-staged packet scatter -> 4096-slot
+  // per-bucket LDS aggregate (kernels_agg3.hip) -> merge counted staged
+  // groups / leftover rows into the slot table (kernels_agg2.hip).
   void two_phase_chunk(const DevBatch& b, int64_t done, int64_t chunk) {
-    const int nbuck = 1 << AGG2_NBUCK_LOG2;
     const DevColumn& key = b.cols.at(key_col_);
     const DevColumn& val = b.cols.at(val_col_);
     const int64_t* keys = (const int64_t*)key.values + done;
     const double* vals = (const double*)val.values + done;
     const uint8_t* kv = key.validity ? key.validity + done / 8 : nullptr;
     const uint8_t* vv = val.validity ? val.validity + done / 8 : nullptr;
+    const int64_t mat = (int64_t)AGG3_NBUCK << AGG3_GRID_LOG2;
 
     if (!d_partkv_) {
-      if (agg2_v3_) {
-        // 24B records + one line of alignment padding per (block,bucket)
-        d_partkv_.alloc(agg2_chunk_max_ * 24 +
-                        ((int64_t)AGG3_NBUCK << AGG3_GRID_LOG2) * 64);
-      } else if (agg2_split_) {
-        d_partkv_.alloc(agg2_chunk_max_ * sizeof(PartKV));
-        d_rowv_.alloc(agg2_chunk_max_ * 4);
-      } else {
-        d_partkv_.alloc(agg2_chunk_max_ * sizeof(PartRow));
-      }
+      // 24B records + one line of alignment padding per (block,bucket)
+      d_partkv_.alloc(agg2_chunk_max_ * 24 + mat * 64);
       d_leftover_.alloc(agg2_chunk_max_ * sizeof(PartRow));
-      int64_t mat = (int64_t)nbuck << AGG2_GRID_LOG2_MAX;
       d_counts_.alloc((mat + 1) * 4);   // +1: scan total slot
       d_scanned_.alloc((mat + 1) * 4);
-      d_offsets_.alloc((nbuck + 1) * 4);
-      if (agg2_v3_) d_linesz_.alloc((mat + 1) * 4);
+      d_linesz_.alloc((mat + 1) * 4);
       size_t tb = 0;
-      scan_counts_matrix(d_counts_.get<uint32_t>(), d_scanned_.get<uint32_t>(),
+      scan_counts_matrix(d_linesz_.get<uint32_t>(), d_scanned_.get<uint32_t>(),
                          mat + 1, nullptr, &tb, stream_);
       d_scan_tmp_.alloc(tb);
-      d_staged_.alloc(std::max<int64_t>((int64_t)nbuck * AGG2_LSLOTS,
-                                        (int64_t)AGG3_NBUCK * 4096) *
-                      sizeof(StagedGroup));
+      d_staged_.alloc(AGG3_STAGED_CAP * sizeof(StagedGroup));
       d_counters_.alloc(24);  // staged_n, lo_n, special_rows
-      // layout: counts[nbuck+1] | offs[nbuck+1] | counters[2] (8-aligned)
-      pinned_agg2_.alloc(2 * (size_t)(nbuck + 1) * 4 + 64);
+      // layout: counters[3] u64 (copy of d_counters_) | num_groups u64
+      pinned_agg2_.alloc(32);
     }
     hipEvent_t e0, e1;
     AURON_HIP(hipEventCreate(&e0));
     AURON_HIP(hipEventCreate(&e1));
     AURON_HIP(hipEventRecord(e0, stream_));
-    // P1: per-block histogram matrix (+ special-row count). ONE host sync
-    // per chunk: the scan total feeds the offsets kernel on-device, and the
-    // special/staged/leftover counters are read back together after phase A.
+    // ONE host sync per chunk: the special/staged/leftover counters are read
+    // back together after the bucket aggregation.
     AURON_HIP(hipMemsetAsync(d_counters_.get(), 0, 24, stream_));
-    if (agg2_v3_) {
-      // v3: hist -> line-padded scan -> LDS-staged packet scatter -> 4096-
-      // slot bucket aggregation (kernels_agg3.hip)
-      int64_t mat3 = (int64_t)AGG3_NBUCK << AGG3_GRID_LOG2;
-      // adaptive packed-16B records: chunk 1 runs the 24B layout while the
-      // hist probes the normal-key min/max; if the observed range fits u32,
-      // later chunks store (key - base) u32 — 33% less partition traffic.
-      // Out-of-range keys in later chunks take the counted leftover bypass,
-      // so the choice is a pure optimization, never a correctness bet.
-      if (agg2_p16_en_ && !agg2_v4_ && !p16_decided_) {
-        // one-time key-range probe (8 B/row) so even the FIRST chunk runs
-        // the packed layout; ~0.35 ms vs ~2.8 ms saved on a 256M chunk
-        if (!d_kminmax_) d_kminmax_.alloc(16);
-        AURON_HIP(hipMemsetAsync(d_kminmax_.get(), 0xFF, 8, stream_));
-        AURON_HIP(hipMemsetAsync(d_kminmax_.get<uint8_t>() + 8, 0, 8,
-                                 stream_));
-        launch_keys_minmax(keys, kv, chunk,
-                           d_kminmax_.get<unsigned long long>(), stream_);
-        uint64_t h_kmm[2];
-        AURON_HIP(hipMemcpyAsync(h_kmm, d_kminmax_.get(), 16,
-                                 hipMemcpyDeviceToHost, stream_));
-        AURON_HIP(hipStreamSynchronize(stream_));
-        p16_decided_ = true;
-        if (h_kmm[0] <= h_kmm[1] && h_kmm[1] - h_kmm[0] <= 0xFFFFFFFFull) {
-          packed16_ = true;
-          key_base16_ = (int64_t)(h_kmm[0] ^ 0x8000000000000000ull);
-          DBG("agg.p16 enabled: key range %llu",
-              (unsigned long long)(h_kmm[1] - h_kmm[0]));
-        }
+    // adaptive packed-16B records: if the normal-key range fits u32, chunks
+    // store (key - base) u32 — 33% less partition traffic. Out-of-range keys
+    // in later chunks take the counted leftover bypass, so the choice is a
+    // pure optimization, never a correctness bet.
+    if (agg2_p16_en_ && !p16_decided_) {
+      // one-time key-range probe (8 B/row) so even the FIRST chunk runs
+      // the packed layout; ~0.35 ms vs ~2.8 ms saved on a 256M chunk
+      if (!d_kminmax_) d_kminmax_.alloc(16);
+      AURON_HIP(hipMemsetAsync(d_kminmax_.get(), 0xFF, 8, stream_));
+      AURON_HIP(hipMemsetAsync(d_kminmax_.get<uint8_t>() + 8, 0, 8, stream_));
+      launch_keys_minmax(keys, kv, chunk,
+                         d_kminmax_.get<unsigned long long>(), stream_);
+      uint64_t h_kmm[2];
+      AURON_HIP(hipMemcpyAsync(h_kmm, d_kminmax_.get(), 16,
+                               hipMemcpyDeviceToHost, stream_));
+      AURON_HIP(hipStreamSynchronize(stream_));
+      p16_decided_ = true;
+      if (h_kmm[0] <= h_kmm[1] && h_kmm[1] - h_kmm[0] <= 0xFFFFFFFFull) {
+        packed16_ = true;
+        key_base16_ = (int64_t)(h_kmm[0] ^ 0x8000000000000000ull);
+        DBG("agg.p16 enabled: key range %llu",
+            (unsigned long long)(h_kmm[1] - h_kmm[0]));
       }
-      const int rec3 = (packed16_ && !agg2_v4_) ? 16 : 24;
-      // the v4 workers cover the same 1024-wide virtual-lane tiles as the
-      // 1024-thread hist, so the hist launch is identical for v3 and v4
-      launch_agg2_hist(keys, kv, chunk, AGG3_NBUCK_LOG2, AGG3_GRID_LOG2,
-                       d_counts_.get<uint32_t>(),
-                       (uint32_t*)(d_counters_.get<uint8_t>() + 16), 1024,
-                       stream_);
-      launch_agg3_line_sizes(d_counts_.get<uint32_t>(), mat3 + 1,
-                             d_linesz_.get<uint32_t>(), rec3, stream_);
-      size_t tb3 = d_scan_tmp_.size();
-      scan_counts_matrix(d_linesz_.get<uint32_t>(),
-                         d_scanned_.get<uint32_t>(), mat3 + 1,
-                         d_scan_tmp_.get(), &tb3, stream_);
-      if (agg2_v4_)
-        launch_agg4_scatter(keys, kv, vals, vv, chunk, AGG3_NBUCK_LOG2,
-                            AGG3_GRID_LOG2, d_scanned_.get<uint32_t>(),
-                            d_partkv_.get<uint8_t>(),
-                            d_leftover_.get<PartRow>(),
-                            d_counters_.get<unsigned long long>() + 1,
-                            d_linesz_.get<uint32_t>(), t_.error_flag, stream_);
-      else
-        launch_agg3_scatter(keys, kv, vals, vv, chunk, AGG3_NBUCK_LOG2,
-                            AGG3_GRID_LOG2, d_scanned_.get<uint32_t>(),
-                            d_partkv_.get<uint8_t>(),
-                            d_leftover_.get<PartRow>(),
-                            d_counters_.get<unsigned long long>() + 1,
-                            d_linesz_.get<uint32_t>(),  // free after the scan
-                            t_.error_flag, rec3, key_base16_, stream_);
-      launch_agg3_bucket(d_partkv_.get<uint8_t>(), d_counts_.get<uint32_t>(),
-                         d_linesz_.get<uint32_t>(),
-                         d_scanned_.get<uint32_t>(), AGG3_GRID_LOG2,
-                         val_is_int_ ? 1 : 0, AGG3_NBUCK,
-                         d_staged_.get<StagedGroup>(),
-                         d_counters_.get<unsigned long long>(),
-                         (int64_t)AGG3_NBUCK * 4096,
-                         d_leftover_.get<PartRow>(),
-                         d_counters_.get<unsigned long long>() + 1,
-                         t_.error_flag, rec3, key_base16_, stream_);
-    } else {
-    int64_t mat = (int64_t)nbuck << agg2_grid_log2_;
-    launch_agg2_hist(keys, kv, chunk, AGG2_NBUCK_LOG2, agg2_grid_log2_,
-                     d_counts_.get<uint32_t>(),
-                     (uint32_t*)(d_counters_.get<uint8_t>() + 16), agg2_block_,
-                     stream_);
-    size_t tb = d_scan_tmp_.size();
-    scan_counts_matrix(d_counts_.get<uint32_t>(), d_scanned_.get<uint32_t>(),
-                       mat + 1, d_scan_tmp_.get(), &tb, stream_);
-    launch_agg2_offsets(d_scanned_.get<uint32_t>(), AGG2_NBUCK_LOG2,
-                        agg2_grid_log2_, d_offsets_.get<uint32_t>(), stream_);
-    // P2: scatter
-    if (agg2_split_)
-      launch_agg2_scatter(keys, kv, vals, vv, chunk, AGG2_NBUCK_LOG2,
-                          agg2_grid_log2_, d_scanned_.get<uint32_t>(),
-                          d_partkv_.get<PartKV>(), d_rowv_.get<uint32_t>(),
-                          agg2_block_, stream_);
-    else
-      launch_agg2_scatter24(keys, kv, vals, vv, chunk, AGG2_NBUCK_LOG2,
-                            agg2_grid_log2_, d_scanned_.get<uint32_t>(),
-                            d_partkv_.get<PartRow>(), agg2_block_, stream_);
-    // A: per-bucket LDS aggregation (counters zeroed above; staged_n at +0,
-    // lo_n at +1, special count at byte offset 8 via the +2 uint32 slot)
-    if (agg2_split_)
-      launch_agg2_bucket(d_partkv_.get<PartKV>(), d_rowv_.get<uint32_t>(),
-                         d_offsets_.get<uint32_t>(), val_is_int_ ? 1 : 0,
-                         nbuck, d_staged_.get<StagedGroup>(),
-                         d_counters_.get<unsigned long long>(),
-                         (int64_t)nbuck * AGG2_LSLOTS,
-                         d_leftover_.get<PartRow>(),
-                         d_counters_.get<unsigned long long>() + 1,
-                         t_.error_flag, agg2_block_, stream_);
-    else
-      launch_agg2_bucket24(d_partkv_.get<PartRow>(),
-                           d_offsets_.get<uint32_t>(), val_is_int_ ? 1 : 0,
-                           nbuck, d_staged_.get<StagedGroup>(),
-                           d_counters_.get<unsigned long long>(),
-                           (int64_t)nbuck * AGG2_LSLOTS,
-                           d_leftover_.get<PartRow>(),
-                           d_counters_.get<unsigned long long>() + 1,
-                           t_.error_flag, agg2_block_, stream_);
     }
-    unsigned long long* h_ctr =
-        (unsigned long long*)(pinned_agg2_.get<uint8_t>() +
-                              2 * (size_t)(nbuck + 1) * 4);
+    const int rec = packed16_ ? 16 : 24;
+    launch_agg2_hist(keys, kv, chunk, AGG3_NBUCK_LOG2, AGG3_GRID_LOG2,
+                     d_counts_.get<uint32_t>(),
+                     (uint32_t*)(d_counters_.get<uint8_t>() + 16), stream_);
+    launch_agg3_line_sizes(d_counts_.get<uint32_t>(), mat + 1,
+                           d_linesz_.get<uint32_t>(), rec, stream_);
+    size_t tb = d_scan_tmp_.size();
+    scan_counts_matrix(d_linesz_.get<uint32_t>(), d_scanned_.get<uint32_t>(),
+                       mat + 1, d_scan_tmp_.get(), &tb, stream_);
+    launch_agg3_scatter(keys, kv, vals, vv, chunk, AGG3_NBUCK_LOG2,
+                        AGG3_GRID_LOG2, d_scanned_.get<uint32_t>(),
+                        d_partkv_.get<uint8_t>(), d_leftover_.get<PartRow>(),
+                        d_counters_.get<unsigned long long>() + 1,
+                        d_linesz_.get<uint32_t>(),  // free after the scan
+                        t_.error_flag, rec, key_base16_, stream_);
+    launch_agg3_bucket(d_partkv_.get<uint8_t>(), d_counts_.get<uint32_t>(),
+                       d_linesz_.get<uint32_t>(), d_scanned_.get<uint32_t>(),
+                       AGG3_GRID_LOG2, val_is_int_ ? 1 : 0, AGG3_NBUCK,
+                       d_staged_.get<StagedGroup>(),
+                       d_counters_.get<unsigned long long>(), AGG3_STAGED_CAP,
+                       d_leftover_.get<PartRow>(),
+                       d_counters_.get<unsigned long long>() + 1,
+                       t_.error_flag, rec, key_base16_, stream_);
+    unsigned long long* h_ctr = pinned_agg2_.get<unsigned long long>();
     AURON_HIP(hipMemcpyAsync(h_ctr, d_counters_.get(), 24,
                              hipMemcpyDeviceToHost, stream_));
     uint64_t* h_ng = (uint64_t*)(h_ctr + 3);
@@ -2052,47 +1782,18 @@ class AggOp {
     if (special_rows)
       launch_agg2_specials(t_, keys, kv, vals, vv, chunk, row_cursor_, stream_);
     // true cardinality from the piggybacked pre-merge read (no extra sync);
-    // the piecewise loops below grow the bound as they merge
+    // the piecewise merges below grow the bound as they go
     ng_true_ = *h_ng;
     ng_bound_ = *h_ng + (special_rows ? 2u : 0u);
-    // merge: table inserts bounded by the COUNTED lists; piecewise so a
-    // VRAM budget (spill) smaller than the staged list still works
-    for (int64_t done2 = 0; done2 < staged_n;) {
-      ensure_capacity((int64_t)ng_bound_ + std::min<int64_t>(
-                                               staged_n - done2, 1 << 20));
-      int64_t free2 = t_.cap * 3 / 4 - (int64_t)ng_bound_;
-      if (free2 < (1 << 14)) {
-        refresh_ng();
-        free2 = t_.cap * 3 / 4 - (int64_t)ng_true_;
-        if (free2 < (1 << 14)) {
-          spill_table();
-          continue;
-        }
-      }
-      int64_t piece = std::min(staged_n - done2, free2);
-      launch_agg2_merge_groups(t_, d_staged_.get<StagedGroup>() + done2, piece,
+    // merge: table inserts bounded by the COUNTED lists
+    merge_counted(staged_n, [&](int64_t at, int64_t piece) {
+      launch_agg2_merge_groups(t_, d_staged_.get<StagedGroup>() + at, piece,
                                row_cursor_, stream_);
-      done2 += piece;
-      ng_bound_ += (uint64_t)piece;
-    }
-    for (int64_t done2 = 0; done2 < lo_n;) {
-      ensure_capacity((int64_t)ng_bound_ +
-                      std::min<int64_t>(lo_n - done2, 1 << 20));
-      int64_t free2 = t_.cap * 3 / 4 - (int64_t)ng_bound_;
-      if (free2 < (1 << 14)) {
-        refresh_ng();
-        free2 = t_.cap * 3 / 4 - (int64_t)ng_true_;
-        if (free2 < (1 << 14)) {
-          spill_table();
-          continue;
-        }
-      }
-      int64_t piece = std::min(lo_n - done2, free2);
-      launch_agg2_leftovers(t_, d_leftover_.get<PartRow>() + done2, piece,
+    });
+    merge_counted(lo_n, [&](int64_t at, int64_t piece) {
+      launch_agg2_leftovers(t_, d_leftover_.get<PartRow>() + at, piece,
                             row_cursor_, stream_);
-      done2 += piece;
-      ng_bound_ += (uint64_t)piece;
-    }
+    });
     AURON_HIP(hipEventRecord(e1, stream_));
     ev_pairs_.push_back({e0, e1});
     update_rows_ += chunk;
@@ -2795,27 +2496,14 @@ class AggOp {
   DevBuf d_ckey_, d_cprio_, d_cval_, d_cn_, d_cskey_, d_csval_;
   PinnedBuf pinned_meta_, pinned_emit_;
   // two-phase scratch (allocated on first large chunk)
-  bool agg2_split_ = false;
-  bool agg2_v3_ = true;
-  bool agg2_v4_ = false;
   bool agg2_p16_en_ = true;   // AURON_AGG2_P16=0 disables the adaptive path
-  bool p16_decided_ = false;  // one hist range probe (chunk 1)
-  bool packed16_ = false;     // later chunks use 16B partition records
+  bool p16_decided_ = false;  // one key-range probe (chunk 1)
+  bool packed16_ = false;     // chunks use 16B partition records
   int64_t key_base16_ = 0;
   DevBuf d_kminmax_;
-  bool agg2_pipe_ = false;
   bool agg2_conf_read_ = false;
-  int agg2_grid_log2_ = 9;
-  int agg2_block_ = 1024;
-  DevBuf d_partkv_, d_rowv_, d_leftover_, d_counts_, d_scanned_, d_scan_tmp_, d_offsets_,
+  DevBuf d_partkv_, d_leftover_, d_counts_, d_scanned_, d_scan_tmp_,
       d_staged_, d_counters_, d_linesz_;
-  // cross-chunk pipeline scratch (double-buffered) + aux stream
-  DevBuf d_ppart_[2], d_pleft_[2], d_pcounts_[2], d_plinesz_[2],
-      d_pscanned_[2], d_pctr_[2], d_pscan_tmp_;
-  PinnedBuf pin_pctr_[2];
-  hipStream_t s_aux_ = nullptr;
-  hipEvent_t ev_scatter_[2] = {}, ev_merge_[2] = {}, ev_read_[2] = {},
-             ev_pipe_[1] = {};
   PinnedBuf pinned_agg2_;
   std::vector<DevBatch> held_, skipped_;
 };

@@ -278,17 +278,8 @@ struct StagedGroup {
   double sum;
   unsigned long long cnt_first;  // cnt<<32 | chunk-local first_row
 };
-// partitioned row records. The hot streams are split 16B + 4B: the {key,val}
-// pair is one aligned 16-byte store (4 per cache line, never straddling),
-// the rowv stream coalesces as plain dwords — 20 B/row vs the 24 B padded
-// AoS record (measured faster), while still touching at most two line runs
-// per row (the original 3×8B SoA split made scatter 64% of GPU time).
-struct PartKV {
-  int64_t key;
-  double val;
-};
-static_assert(sizeof(PartKV) == 16, "PartKV must be 16 bytes");
-// leftover rows (LDS-window overflow) keep the self-contained AoS record
+// leftover rows (LDS-window overflow, scatter bypass): self-contained AoS
+// record, the same field order as the 24-byte partition record
 struct PartRow {
   int64_t key;
   double val;
@@ -296,47 +287,23 @@ struct PartRow {
   uint32_t _pad;
 };
 static_assert(sizeof(PartRow) == 24, "PartRow must be 24 bytes");
-constexpr int AGG2_LSLOTS = 2048;  // LDS table entries per bucket
 
-constexpr int AGG2_GRID_LOG2_MAX = 10;  // matrix sizing bound for the
-                                        // runtime-tunable hist/scatter grid
+// bounds the scatter grid (1 << grid_log2 blocks): k_agg3_bucket keeps one
+// cumulative count per scatter block in a cum[1 << AGG2_GRID_LOG2_MAX] LDS
+// array (4 KB), so grid_log2 must not exceed it
+constexpr int AGG2_GRID_LOG2_MAX = 10;
 // per-BLOCK bucket histogram into the bucket-major counts matrix
-// [nbuck << AGG2_GRID_LOG2]
+// [nbuck << grid_log2]; 1024-thread blocks, the scatter's row traversal
 void launch_agg2_hist(const int64_t* keys, const uint8_t* key_valid, int64_t n,
                       int nbuck_log2, int grid_log2, uint32_t* counts_matrix,
-                      uint32_t* special_rows, int block, hipStream_t s,
-                      unsigned long long* kminmax = nullptr);
+                      uint32_t* special_rows, hipStream_t s);
 // exclusive scan over the flat counts matrix -> per-(block,bucket) bases
 void scan_counts_matrix(const uint32_t* counts, uint32_t* scanned, int64_t n,
                         void* temp, size_t* temp_bytes, hipStream_t s);
-void launch_agg2_offsets(const uint32_t* scanned, int nbuck_log2,
-                         int grid_log2, uint32_t* offsets, hipStream_t s);
-void launch_agg2_scatter(const int64_t* keys, const uint8_t* key_valid,
-                         const double* vals, const uint8_t* val_valid,
-                         int64_t n, int nbuck_log2, int grid_log2,
-                         const uint32_t* scanned,
-                         PartKV* out_kv, uint32_t* out_rowv, int block,
-                         hipStream_t s);
-void launch_agg2_scatter24(const int64_t* keys, const uint8_t* key_valid,
-                           const double* vals, const uint8_t* val_valid,
-                           int64_t n, int nbuck_log2, int grid_log2,
-                           const uint32_t* scanned,
-                           PartRow* out, int block, hipStream_t s);
-void launch_agg2_bucket24(const PartRow* part, const uint32_t* offsets,
-                          int is_int, int nbuckets, StagedGroup* staged,
-                          unsigned long long* staged_n, int64_t staged_cap,
-                          PartRow* leftover, unsigned long long* lo_n,
-                          uint32_t* error_flag, int block, hipStream_t s);
 void launch_agg2_specials(const AggTable& t, const int64_t* keys,
                           const uint8_t* key_valid, const double* vals,
                           const uint8_t* val_valid, int64_t n,
                           uint64_t row_offset, hipStream_t s);
-void launch_agg2_bucket(const PartKV* part_kv, const uint32_t* part_rowv,
-                        const uint32_t* offsets, int is_int,
-                        int nbuckets, StagedGroup* staged,
-                        unsigned long long* staged_n, int64_t staged_cap,
-                        PartRow* leftover, unsigned long long* lo_n,
-                        uint32_t* error_flag, int block, hipStream_t s);
 void launch_agg2_merge_groups(const AggTable& t, const StagedGroup* staged,
                               int64_t n, uint64_t row_offset, hipStream_t s);
 void launch_agg2_leftovers(const AggTable& t, const PartRow* rows, int64_t n,
@@ -548,18 +515,6 @@ void launch_agg3_scatter(const int64_t* keys, const uint8_t* key_valid,
                          PartRow* leftover, unsigned long long* lo_n,
                          uint32_t* bypass_matrix, uint32_t* err_flag,
                          int rec, int64_t key_base, hipStream_t s);
-// v4 scatter: barrier-free per-bucket LDS rings drained by dedicated
-// flusher waves (same in/out contract as launch_agg3_scatter). The hist
-// feeding it must run with agg4_worker_waves()*64 threads per block so the
-// row->block mapping matches the v4 worker traversal.
-int agg4_worker_waves();
-void launch_agg4_scatter(const int64_t* keys, const uint8_t* key_valid,
-                         const double* vals, const uint8_t* val_valid,
-                         int64_t n, int nbuck_log2, int grid_log2,
-                         const uint32_t* line_scan, uint8_t* out,
-                         PartRow* leftover, unsigned long long* lo_n,
-                         uint32_t* bypass_matrix, uint32_t* err_flag,
-                         hipStream_t s);
 void launch_agg3_bucket(const uint8_t* part, const uint32_t* counts,
                         const uint32_t* bypass,
                         const uint32_t* line_scan, int grid_log2, int is_int,

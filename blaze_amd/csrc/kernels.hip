@@ -25,17 +25,9 @@
 
 #include "kernels.h"
 #include "dev_agg.h"
+#include "launch_check.h"
 
 namespace auron {
-
-// raise launch-configuration errors loudly (hipLaunchKernelGGL itself
-// reports nothing)
-static inline void check_launch(const char* name) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess)
-    throw std::runtime_error(std::string("kernel launch failed: ") + name +
-                             ": " + hipGetErrorString(e));
-}
 
 static constexpr int BLOCK = 256;
 static constexpr int64_t MAX_BLOCKS = 256 * 8;

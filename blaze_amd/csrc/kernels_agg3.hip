@@ -19,44 +19,12 @@
 #include <hip/hip_runtime.h>
 
 #include <stdexcept>
-#include <string>
 
+#include "dev_agg.h"
 #include "kernels.h"
+#include "launch_check.h"
 
 namespace auron {
-
-namespace {
-inline void check_launch3(const char* name) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess)
-    throw std::runtime_error(std::string("kernel launch failed: ") + name +
-                             ": " + hipGetErrorString(e));
-}
-constexpr int64_t KEY_EMPTY3 = INT64_MIN;
-
-__device__ __forceinline__ uint64_t mix64_3(uint64_t x) {
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
-
-__device__ __forceinline__ bool bit_get3(const uint8_t* bm, int64_t i) {
-  return (bm[i >> 3] >> (i & 7)) & 1;
-}
-
-__device__ __forceinline__ void sum_accum3(double* acc, double v,
-                                           bool is_int) {
-  if (is_int) {
-    uint64_t b;
-    memcpy(&b, &v, 8);
-    atomicAdd(reinterpret_cast<unsigned long long*>(acc),
-              (unsigned long long)b);
-  } else {
-    unsafeAtomicAdd(acc, v);
-  }
-}
-}  // namespace
 
 // ---- byte-line offsets: pad each (block,bucket) range to whole 64B lines --
 // line_sizes[i] = ceil(counts[i] * 24 / 64): the exclusive scan of THIS
@@ -74,7 +42,7 @@ void launch_agg3_line_sizes(const uint32_t* counts, int64_t n,
                             uint32_t* sizes, int rec, hipStream_t s) {
   hipLaunchKernelGGL(k_agg3_line_sizes, dim3(256), dim3(256), 0, s, counts, n,
                      (uint32_t)rec, sizes);
-  check_launch3("k_agg3_line_sizes");
+  check_launch("k_agg3_line_sizes");
 }
 
 // ---- v3 scatter ------------------------------------------------------------
@@ -118,9 +86,9 @@ __global__ void k_keys_minmax(const int64_t* __restrict__ keys,
   unsigned long long kmin = ~0ull, kmax = 0ull;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * blockDim.x) {
-    if (key_valid && !bit_get3(key_valid, i)) continue;
+    if (key_valid && !bit_get_dev(key_valid, i)) continue;
     int64_t k = keys[i];
-    if (k == KEY_EMPTY3) continue;
+    if (k == KEY_EMPTY) continue;
     unsigned long long m = (unsigned long long)k ^ 0x8000000000000000ull;
     kmin = m < kmin ? m : kmin;
     kmax = m > kmax ? m : kmax;
@@ -136,7 +104,7 @@ void launch_keys_minmax(const int64_t* keys, const uint8_t* key_valid,
                         hipStream_t s) {
   hipLaunchKernelGGL(k_keys_minmax, dim3(512), dim3(256), 0, s, keys,
                      key_valid, n, kminmax);
-  check_launch3("k_keys_minmax");
+  check_launch("k_keys_minmax");
 }
 
 // REC = 24: [i64 key][f64 val][u32 rowv] (pad to 24). REC = 16: the key is
@@ -212,13 +180,13 @@ __global__ void __launch_bounds__(1024) k_agg3_scatter(
       mine = 1;
       int64_t k = k_cur[r];
       bool advanced = false;
-      bool knull = key_valid && !bit_get3(key_valid, my[r]);
-      if (knull || k == KEY_EMPTY3) {
+      bool knull = key_valid && !bit_get_dev(key_valid, my[r]);
+      if (knull || k == KEY_EMPTY) {
         my[r] += step;  // specials handled by k_agg2_specials
         mine |= (my[r] < n);
         advanced = true;
       } else {
-        uint32_t b = (uint32_t)(mix64_3((uint64_t)k) >> (64 - nbuck_log2));
+        uint32_t b = (uint32_t)(mix64((uint64_t)k) >> (64 - nbuck_log2));
         bool range_ok = true;
         uint64_t koff = 0;
         if (REC == 16) {
@@ -228,7 +196,7 @@ __global__ void __launch_bounds__(1024) k_agg3_scatter(
         if (!range_ok) {
           // outside the packed key window: leftover bypass (exactness for
           // any input; the hist counted this row, so correct the matrix)
-          bool vvalid = !val_valid || bit_get3(val_valid, my[r]);
+          bool vvalid = !val_valid || bit_get_dev(val_valid, my[r]);
           unsigned long long p = atomicAdd(lo_n, 1ull);
           leftover[p] = PartRow{
               k, v_cur[r], (uint32_t)my[r] | (vvalid ? 0x80000000u : 0u), 0};
@@ -244,7 +212,7 @@ __global__ void __launch_bounds__(1024) k_agg3_scatter(
         }
         uint32_t pos = atomicAdd(&cnt[b], 1u);
         if (pos < CAP) {
-          bool vvalid = !val_valid || bit_get3(val_valid, my[r]);
+          bool vvalid = !val_valid || bit_get_dev(val_valid, my[r]);
           uint8_t* rec = stage + ((size_t)b * CAP + pos) * REC;
           uint32_t rowv = (uint32_t)my[r] | (vvalid ? 0x80000000u : 0u);
           if (REC == 16) {
@@ -268,7 +236,7 @@ __global__ void __launch_bounds__(1024) k_agg3_scatter(
             // hot bucket (skew): route the row to the leftover list; the
             // histogram already counted it, so record the correction the
             // bucket kernel must subtract from this (block,bucket) range
-            bool vvalid = !val_valid || bit_get3(val_valid, my[r]);
+            bool vvalid = !val_valid || bit_get_dev(val_valid, my[r]);
             unsigned long long p = atomicAdd(lo_n, 1ull);
             leftover[p] = PartRow{
                 k, v_cur[r],
@@ -386,304 +354,7 @@ void launch_agg3_scatter(const int64_t* keys, const uint8_t* key_valid,
     else A3_LAUNCH(2, 24);
   }
 #undef A3_LAUNCH
-  check_launch3("k_agg3_scatter");
-}
-
-// ---- v4 scatter: barrier-free producer/flusher rings -----------------------
-// The v3 tile loop parks waves 73% of the time on its per-tile barriers
-// (SQ_WAIT_ANY ~7x ACTIVE, gpurun_out sq pass). v4 removes every barrier
-// from the hot loop: WORKER waves (AURON_AGG2_V4_WW, default 8 of 16)
-// append records into per-bucket 8-slot LDS rings; the remaining FLUSHER
-// waves (8-lane subgroups, 8 buckets in flight each)
-// continuously drain 4-record 96 B quanta into the same 64B-aligned
-// per-(block,bucket) ranges. Commit protocol: each ring slot carries a
-// sequence TAG (= the absolute ring position) written AFTER the record by
-// the same lane — LDS executes one wave's DS ops in order — so the flusher
-// flushes exactly the contiguous committed prefix, tolerating out-of-order
-// commits across workers. Hot buckets bypass to the leftover list BEFORE
-// reserving (the reservation sequence must stay dense), with the same
-// per-(block,bucket) correction matrix as v3.
-static constexpr int A4_RING = 8;   // ring slots per bucket (pow2)
-static constexpr int A4_QUANT = 8;  // records per flush quantum (192 B —
-                                    // one full ring; halves flusher visits
-                                    // per record vs the 96 B quantum)
-
-#define A4_LD_RLX(p) \
-  __hip_atomic_load((p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)
-#define A4_LD_ACQ(p) \
-  __hip_atomic_load((p), __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP)
-#define A4_ST_REL(p, v) \
-  __hip_atomic_store((p), (v), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP)
-// LDS-only release: wait the wave's outstanding DS ops, then a relaxed
-// store. A generic workgroup-scope RELEASE also emits s_waitcnt vmcnt(0),
-// which stalls ~800 cycles for in-flight HBM stores/prefetches that are
-// irrelevant to LDS ring reuse — measured as the v4 flusher bottleneck.
-#define A4_ST_REL_LDS(p, v)                        \
-  do {                                             \
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); \
-    __hip_atomic_store((p), (v), __ATOMIC_RELAXED, \
-                       __HIP_MEMORY_SCOPE_WORKGROUP); \
-  } while (0)
-
-__global__ void __launch_bounds__(1024) k_agg4_scatter(
-    const int64_t* __restrict__ keys, const uint8_t* __restrict__ key_valid,
-    const double* __restrict__ vals, const uint8_t* __restrict__ val_valid,
-    int64_t n, int nbuck_log2, int grid_log2, int worker_waves,
-    const uint32_t* __restrict__ line_scan, uint8_t* __restrict__ out,
-    PartRow* __restrict__ leftover, unsigned long long* __restrict__ lo_n,
-    uint32_t* __restrict__ bypass_matrix, uint32_t* __restrict__ err_flag) {
-  const uint32_t nbuck = 1u << nbuck_log2;
-  extern __shared__ uint8_t lds[];
-  // layout: ring[nbuck][A4_RING][24] | tag[nbuck][A4_RING] u32 |
-  //         cnt[nbuck] | fl[nbuck] | base_line[nbuck] | byp[nbuck] | done
-  uint8_t* ring = lds;
-  uint32_t* tag = (uint32_t*)(lds + (size_t)nbuck * A4_RING * 24);
-  uint32_t* cnt = tag + (size_t)nbuck * A4_RING;
-  uint32_t* fl = cnt + nbuck;
-  uint32_t* base_line = fl + nbuck;
-  uint32_t* byp = base_line + nbuck;
-  uint32_t* done = byp + nbuck;
-
-  for (uint32_t b = threadIdx.x; b < nbuck; b += blockDim.x) {
-    cnt[b] = 0;
-    fl[b] = 0;
-    byp[b] = 0;
-    base_line[b] = line_scan[((size_t)b << grid_log2) | blockIdx.x];
-  }
-  for (uint32_t i = threadIdx.x; i < nbuck * A4_RING; i += blockDim.x)
-    tag[i] = 0xFFFFFFFFu;  // != any pos; never reset (successive uses of a
-                           // slot carry distinct pos values: pos = slot mod 8)
-  if (threadIdx.x == 0) *done = 0;
-  __syncthreads();
-
-  const int wave = (int)(threadIdx.x >> 6);
-  const int lane = (int)(threadIdx.x & 63);
-  const int nwave = (int)(blockDim.x >> 6);
-
-  if (wave < worker_waves) {
-    // ---- worker: append rows; no barriers. VIRTUAL-LANE row mapping: rows
-    // are credited to blocks by the 1024-thread histogram stride, so worker
-    // thread t covers virtual lanes {t, t+NW, ...} < 1024 of each tile —
-    // the hist keeps its full 1024-thread launch (384-thread hist measured
-    // 2.2x slower), and each worker carries 2-3 rows per tile of ILP.
-    //
-    // A lane that reserved a ring position it cannot yet write (backlog)
-    // must NOT spin in an inner loop: divergent serialization would park
-    // its sibling lanes, including ones holding the very positions the
-    // flusher needs next — an intra-wave deadlock (measured: spin-bound
-    // trips under skew/bursts). Reservations it cannot complete go into a
-    // small per-lane pending FIFO retried once per pass (leftover-bypass
-    // when full), so every lane makes bounded attempts and siblings always
-    // progress.
-    const int NW = worker_waves * 64;
-    const int tid = (int)threadIdx.x;
-    const int64_t tile_stride = (int64_t)gridDim.x << 10;
-    constexpr int MAXSUB = 3;   // ceil(1024 / (6 waves * 64))
-    constexpr int PCAP = 4;     // pending FIFO slots (pow2)
-    int64_t rk[MAXSUB];
-    double rv[MAXSUB];
-    uint32_t rvalid[MAXSUB];    // bit0: in range+normal key; bit1: val valid
-    int64_t rrow[MAXSUB];
-    uint32_t p_b[PCAP], p_pos[PCAP], p_rowv[PCAP];
-    int64_t p_k[PCAP];
-    double p_v[PCAP];
-    uint32_t p_hd = 0, p_tl = 0;
-    int p_spin = 0;
-    int64_t tb = (int64_t)blockIdx.x << 10;
-    int nr = 0;
-    auto load_tile = [&](int64_t base) {
-      nr = 0;
-      if (base >= n) return;
-#pragma unroll
-      for (int s = 0; s < MAXSUB; s++) {
-        int vt = tid + s * NW;
-        int64_t i2 = base + vt;
-        if (vt < 1024 && i2 < n) {
-          rk[nr] = keys[i2];
-          rv[nr] = vals[i2];
-          bool knull = key_valid && !bit_get3(key_valid, i2);
-          bool vvalid = !val_valid || bit_get3(val_valid, i2);
-          rvalid[nr] = (!knull && rk[nr] != KEY_EMPTY3 ? 1u : 0u) |
-                       (vvalid ? 2u : 0u);
-          rrow[nr] = i2;
-          nr++;
-        }
-      }
-    };
-    auto append = [&](uint32_t b, uint32_t pos, int64_t k, double v,
-                      uint32_t rowv) {
-      uint32_t slot = pos & (A4_RING - 1);
-      uint8_t* rec = ring + ((size_t)b * A4_RING + slot) * 24;
-      *(int64_t*)rec = k;
-      *(double*)(rec + 8) = v;
-      *(uint32_t*)(rec + 16) = rowv;
-      // commit: LDS-only release — the record stores are DS ops,
-      // lgkmcnt(0) fences all 64 lanes of the wave
-      A4_ST_REL_LDS(&tag[b * A4_RING + slot], pos);
-    };
-    load_tile(tb);
-    while (nr > 0 || p_hd != p_tl) {
-      bool progress = false;
-      if (p_hd != p_tl) {  // retry the oldest pending reservation
-        uint32_t q = p_tl & (PCAP - 1);
-        if (p_pos[q] - A4_LD_ACQ(&fl[p_b[q]]) < A4_RING) {
-          append(p_b[q], p_pos[q], p_k[q], p_v[q], p_rowv[q]);
-          p_tl++;
-          p_spin = 0;
-          progress = true;
-        } else if (++p_spin > (1 << 22)) {
-          atomicOr(err_flag, 64u);  // fails the chunk, never hangs the box
-          p_tl = p_hd;
-        }
-      }
-      // process the tile only when the FIFO can absorb every row going
-      // pending — this keeps the reserved-but-unwritable inline spin below
-      // unreachable (an inline spin can deadlock the wave: siblings parked
-      // by divergence may hold the window positions the flusher needs)
-      bool take = (p_hd - p_tl) + (uint32_t)nr <= PCAP;
-      for (int r = 0; take && r < nr; r++) {
-        if (!(rvalid[r] & 1u)) continue;  // special: handled elsewhere
-        int64_t k = rk[r];
-        uint32_t b = (uint32_t)(mix64_3((uint64_t)k) >> (64 - nbuck_log2));
-        uint32_t rowv =
-            (uint32_t)rrow[r] | ((rvalid[r] & 2u) ? 0x80000000u : 0u);
-        // hot-bucket bypass BEFORE reserving (the reservation sequence
-        // must stay dense — a reserved slot can never be abandoned)
-        if (A4_LD_RLX(&cnt[b]) - A4_LD_RLX(&fl[b]) >=
-            A4_RING + A4_RING / 2) {
-          unsigned long long p = atomicAdd(lo_n, 1ull);
-          leftover[p] = PartRow{k, rv[r], rowv, 0};
-          atomicAdd(&byp[b], 1u);
-          continue;
-        }
-        uint32_t pos = atomicAdd(&cnt[b], 1u);
-        if (pos - A4_LD_ACQ(&fl[b]) < A4_RING) {
-          append(b, pos, k, rv[r], rowv);
-        } else {  // backlogged: park in the FIFO (room guaranteed above)
-          uint32_t q = p_hd & (PCAP - 1);
-          p_b[q] = b;
-          p_pos[q] = pos;
-          p_rowv[q] = rowv;
-          p_k[q] = k;
-          p_v[q] = rv[r];
-          p_hd++;
-        }
-      }
-      if (take) {
-        if (nr) progress = true;
-        tb += tile_stride;
-        // prefetch the next tile AFTER the appends: issuing these loads
-        // earlier would drag them into the appends' vmcnt waits
-        load_tile(tb);
-      }
-      // back off only when the WHOLE wave is blocked on ring space
-      if (__ballot(progress) == 0) __builtin_amdgcn_s_sleep(2);
-    }
-    // completion signal: RELEASE pairs with the flusher's ACQUIRE so every
-    // tag committed by this wave is visible once done == worker_waves
-    if (lane == 0)
-      __hip_atomic_fetch_add(done, 1u, __ATOMIC_RELEASE,
-                             __HIP_MEMORY_SCOPE_WORKGROUP);
-  } else {
-    // ---- flusher: 8-lane subgroups drain committed prefixes ----
-    static_assert(A4_RING == 8, "ballot tag check assumes 8-slot rings");
-    const int nfw = nwave - worker_waves;
-    const int sg_global = (wave - worker_waves) * 8 + (lane >> 3);
-    const int sg_w = lane >> 3;  // subgroup within this wave
-    const int sl = lane & 7;
-    const uint32_t sg_stride = (uint32_t)nfw * 8;
-    bool draining = false;
-    // software-pipelined sweep: the (fl, tag) reads for bucket b+stride are
-    // issued while bucket b's copy is in flight, hiding the two dependent
-    // LDS round-trips (~120 cycles) that otherwise bound every visit
-    for (;;) {
-      bool all_done = (A4_LD_ACQ(done) == (uint32_t)worker_waves);
-      uint32_t moved = 0;
-      uint32_t b = (uint32_t)sg_global;
-      uint32_t f = fl[b];  // this sg is the only writer of fl[b]
-      uint32_t t = A4_LD_ACQ(&tag[b * A4_RING +
-                                  ((f + (uint32_t)sl) & (A4_RING - 1))]);
-      while (b < nbuck) {
-        uint32_t b2 = b + sg_stride;
-        // ballot-match all 8 tags read in ONE wave instruction (lane sl
-        // covered slot (f+sl)&7): committed-prefix length for this bucket
-        uint64_t m = __ballot(t == f + (uint32_t)sl);
-        uint32_t bits = (uint32_t)(m >> (sg_w * 8)) & 0xFFu;
-        uint32_t ready = __builtin_ctz(~bits | 0x100u);
-        uint32_t k = draining ? ready : ready & ~(uint32_t)(A4_QUANT - 1);
-        // prefetch the NEXT bucket's fl+tag before this bucket's copy
-        uint32_t f2 = 0, t2 = 0;
-        if (b2 < nbuck) {
-          f2 = fl[b2];
-          t2 = A4_LD_ACQ(&tag[b2 * A4_RING +
-                              ((f2 + (uint32_t)sl) & (A4_RING - 1))]);
-        }
-        if (k) {
-          uint64_t* dst = (uint64_t*)(out + ((size_t)base_line[b] << 6) +
-                                      (size_t)f * 24);
-          const uint64_t* src =
-              (const uint64_t*)(ring + (size_t)b * A4_RING * 24);
-          for (uint32_t d = sl; d < k * 3; d += 8) {
-            uint32_t r = d / 3;
-            uint32_t slot = (f + r) & (A4_RING - 1);
-            dst[d] = src[(size_t)slot * 3 + d % 3];
-          }
-          // LDS-only release: the slot reads must complete before workers
-          // may overwrite them; in-flight HBM stores are irrelevant
-          if (sl == 0) A4_ST_REL_LDS(&fl[b], f + k);
-          moved += k;
-        }
-        b = b2;
-        f = f2;
-        t = t2;
-      }
-      if (draining && moved == 0) break;
-      if (all_done) draining = true;  // final sweeps flush partial quanta
-    }
-  }
-  // every (bucket, block) entry is written by its own block — on EVERY exit
-  // path — so the bucket kernel never reads a stale correction matrix
-  __syncthreads();
-  for (uint32_t b = threadIdx.x; b < nbuck; b += blockDim.x)
-    bypass_matrix[((size_t)b << grid_log2) | blockIdx.x] = byp[b];
-}
-
-// The histogram MUST be launched with agg4_worker_waves()*64 threads per
-// block when the v4 scatter consumes its counts: the per-(block,bucket)
-// ranges are credited by the hist's row->block grid-stride mapping, and the
-// v4 workers traverse rows with exactly that stride.
-int agg4_worker_waves() {
-  static int ww = [] {
-    const char* e = getenv("AURON_AGG2_V4_WW");
-    int v = e ? atoi(e) : 8;  // measured optimum: flusher-throughput-bound
-    return (v >= 6 && v <= 15) ? v : 8;
-  }();
-  return ww;
-}
-
-void launch_agg4_scatter(const int64_t* keys, const uint8_t* key_valid,
-                         const double* vals, const uint8_t* val_valid,
-                         int64_t n, int nbuck_log2, int grid_log2,
-                         const uint32_t* line_scan, uint8_t* out,
-                         PartRow* leftover, unsigned long long* lo_n,
-                         uint32_t* bypass_matrix, uint32_t* err_flag,
-                         hipStream_t s) {
-  const uint32_t nbuck = 1u << nbuck_log2;
-  size_t lds = (size_t)nbuck * A4_RING * 24 + (size_t)nbuck * A4_RING * 4 +
-               (size_t)nbuck * 16 + 64;
-  if (lds > 160 * 1024)
-    throw std::runtime_error("agg4 scatter LDS over 160KB");
-  int ww = agg4_worker_waves();
-  hipError_t e = hipFuncSetAttribute(
-      (const void*)k_agg4_scatter,
-      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess)
-    throw std::runtime_error("agg4 scatter LDS attribute failed");
-  hipLaunchKernelGGL(k_agg4_scatter, dim3(1 << grid_log2), dim3(1024), lds, s,
-                     keys, key_valid, vals, val_valid, n, nbuck_log2,
-                     grid_log2, ww, line_scan, out, leftover, lo_n,
-                     bypass_matrix, err_flag);
-  check_launch3("k_agg4_scatter");
+  check_launch("k_agg3_scatter");
 }
 
 // ---- v3 bucket aggregation (4096-slot LDS window, 1024 threads) ------------
@@ -709,7 +380,7 @@ __global__ void __launch_bounds__(1024) k_agg3_bucket(
 
   for (int b = blockIdx.x; b < nbuckets; b += gridDim.x) {
     for (int s = threadIdx.x; s < L3SLOTS; s += blockDim.x) {
-      ls_key[s] = KEY_EMPTY3;
+      ls_key[s] = KEY_EMPTY;
       ls_sum[s] = 0.0;
       ls_cnt[s] = 0;
       ls_first[s] = 0xFFFFFFFFu;
@@ -761,11 +432,11 @@ __global__ void __launch_bounds__(1024) k_agg3_bucket(
           found = (int)h;
           break;
         }
-        if (cur == KEY_EMPTY3) {
+        if (cur == KEY_EMPTY) {
           long long prev = atomicCAS((unsigned long long*)&ls_key[h],
-                                     (unsigned long long)KEY_EMPTY3,
+                                     (unsigned long long)KEY_EMPTY,
                                      (unsigned long long)k);
-          if (prev == (long long)KEY_EMPTY3 || prev == (long long)k) {
+          if (prev == (long long)KEY_EMPTY || prev == (long long)k) {
             found = (int)h;
             break;
           }
@@ -775,7 +446,7 @@ __global__ void __launch_bounds__(1024) k_agg3_bucket(
       if (found >= 0) {
         atomicMin(&ls_first[found], row);
         if (vvalid) {
-          sum_accum3(&ls_sum[found], v, is_int);
+          sum_accum(&ls_sum[found], v, is_int);
           atomicAdd(&ls_cnt[found], 1u);
         }
       } else {
@@ -796,10 +467,10 @@ __global__ void __launch_bounds__(1024) k_agg3_bucket(
       load_rec(r1, &k1, &v1, &rv1);
       load_rec(r2, &k2, &v2, &rv2);
       load_rec(r3, &k3, &v3, &rv3);
-      uint32_t h0 = (uint32_t)mix64_3((uint64_t)k0) & (L3SLOTS - 1);
-      uint32_t h1 = (uint32_t)mix64_3((uint64_t)k1) & (L3SLOTS - 1);
-      uint32_t h2 = (uint32_t)mix64_3((uint64_t)k2) & (L3SLOTS - 1);
-      uint32_t h3 = (uint32_t)mix64_3((uint64_t)k3) & (L3SLOTS - 1);
+      uint32_t h0 = (uint32_t)mix64((uint64_t)k0) & (L3SLOTS - 1);
+      uint32_t h1 = (uint32_t)mix64((uint64_t)k1) & (L3SLOTS - 1);
+      uint32_t h2 = (uint32_t)mix64((uint64_t)k2) & (L3SLOTS - 1);
+      uint32_t h3 = (uint32_t)mix64((uint64_t)k3) & (L3SLOTS - 1);
       resolve(k0, v0, rv0, h0);
       resolve(k1, v1, rv1, h1);
       resolve(k2, v2, rv2, h2);
@@ -811,11 +482,11 @@ __global__ void __launch_bounds__(1024) k_agg3_bucket(
       double v;
       uint32_t rv;
       load_rec(r, &k, &v, &rv);
-      resolve(k, v, rv, (uint32_t)mix64_3((uint64_t)k) & (L3SLOTS - 1));
+      resolve(k, v, rv, (uint32_t)mix64((uint64_t)k) & (L3SLOTS - 1));
     }
     __syncthreads();
     for (int s = threadIdx.x; s < L3SLOTS; s += blockDim.x) {
-      if (ls_key[s] == KEY_EMPTY3) continue;
+      if (ls_key[s] == KEY_EMPTY) continue;
       unsigned long long p = atomicAdd(staged_n, 1ull);
       if ((int64_t)p >= staged_cap) {
         atomicOr(error_flag, 2u);
@@ -848,7 +519,7 @@ void launch_agg3_bucket(const uint8_t* part, const uint32_t* counts,
                        part, counts, bypass, line_scan, grid_log2, is_int,
                        nbuckets, key_base, staged, staged_n, staged_cap,
                        leftover, lo_n, error_flag);
-  check_launch3("k_agg3_bucket");
+  check_launch("k_agg3_bucket");
 }
 
 }  // namespace auron

@@ -19,16 +19,11 @@
 
 #include "dev_agg.h"
 #include "kernels.h"
+#include "launch_check.h"
 
 namespace auron {
 
 namespace {
-inline void check_launchg(const char* name) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess)
-    throw std::runtime_error(std::string("kernel launch failed: ") + name +
-                             ": " + hipGetErrorString(e));
-}
 constexpr int GBLOCK = 256;
 constexpr int64_t GMAX_BLOCKS = 256 * 8;
 inline int ggrid(int64_t n) {
@@ -69,7 +64,7 @@ void launch_hash_fold_bytes(const int32_t* offsets, const uint8_t* data,
                             hipStream_t s) {
   hipLaunchKernelGGL(k_hash_fold_bytes, dim3(ggrid(n)), dim3(GBLOCK), 0, s,
                      offsets, data, valid, n, hashes);
-  check_launchg("k_hash_fold_bytes");
+  check_launch("k_hash_fold_bytes");
 }
 
 // ---- key tuple encoding ----------------------------------------------------
@@ -99,7 +94,7 @@ void launch_gkey_enc_lens(const GKeyCols& c, int64_t n, uint32_t* lens,
                           hipStream_t s) {
   hipLaunchKernelGGL(k_gkey_enc_lens, dim3(ggrid(n)), dim3(GBLOCK), 0, s, c, n,
                      lens);
-  check_launchg("k_gkey_enc_lens");
+  check_launch("k_gkey_enc_lens");
 }
 
 __global__ void k_gkey_enc_write(const GKeyCols c,
@@ -135,7 +130,7 @@ void launch_gkey_enc_write(const GKeyCols& c, const uint32_t* enc_offsets,
                            uint8_t* enc_bytes, int64_t n, hipStream_t s) {
   hipLaunchKernelGGL(k_gkey_enc_write, dim3(ggrid(n)), dim3(GBLOCK), 0, s, c,
                      enc_offsets, enc_bytes, n);
-  check_launchg("k_gkey_enc_write");
+  check_launch("k_gkey_enc_write");
 }
 
 // ---- probe-or-insert -------------------------------------------------------
@@ -245,7 +240,7 @@ void launch_gkey_upsert(const AggTable& t, const GKeyTable& g,
                         hipStream_t s) {
   hipLaunchKernelGGL(k_gkey_upsert, dim3(ggrid(n)), dim3(GBLOCK), 0, s, t, g,
                      enc_offsets, enc_bytes, n, row_offset, slots);
-  check_launchg("k_gkey_upsert");
+  check_launch("k_gkey_upsert");
 }
 
 // ---- slot-indexed accumulate / merge --------------------------------------
@@ -276,7 +271,7 @@ void launch_gkey_update_idx(const AggTable& t, const uint32_t* slots,
                             int64_t n, hipStream_t s) {
   hipLaunchKernelGGL(k_gkey_update_idx, dim3(ggrid(n)), dim3(GBLOCK), 0, s, t,
                      slots, vals, val_valid, n);
-  check_launchg("k_gkey_update_idx");
+  check_launch("k_gkey_update_idx");
 }
 
 __global__ void k_gkey_merge_frozen_idx(const AggTable t,
@@ -306,7 +301,7 @@ void launch_gkey_merge_frozen_idx(const AggTable& t, const uint32_t* slots,
                                   uint32_t layout, hipStream_t s) {
   hipLaunchKernelGGL(k_gkey_merge_frozen_idx, dim3(ggrid(n)), dim3(GBLOCK), 0,
                      s, t, slots, acc_data, acc_offsets, n, layout);
-  check_launchg("k_gkey_merge_frozen_idx");
+  check_launch("k_gkey_merge_frozen_idx");
 }
 
 // ---- growth: re-probe every occupied src slot into dst by stored hash ------
@@ -367,7 +362,7 @@ void launch_gkey_rebuild(const AggTable& dst, const GKeyTable& dg,
                          hipStream_t s) {
   hipLaunchKernelGGL(k_gkey_rebuild, dim3(ggrid(src.cap)), dim3(GBLOCK), 0, s,
                      dst, dg, src, sg);
-  check_launchg("k_gkey_rebuild");
+  check_launch("k_gkey_rebuild");
 }
 
 // ---- emit: decode grouping columns from the pool ---------------------------
@@ -423,7 +418,7 @@ void launch_gkey_out_fixed(const GKeyTable& g, const uint32_t* order_slots,
   hipLaunchKernelGGL(k_gkey_out_fixed, dim3(ggrid((n + 7) / 8)), dim3(GBLOCK),
                      0, s, g, order_slots, n, dts, ncols, col, values,
                      valid_bitmap);
-  check_launchg("k_gkey_out_fixed");
+  check_launch("k_gkey_out_fixed");
 }
 
 __global__ void k_gkey_out_lens(const GKeyTable g,
@@ -457,7 +452,7 @@ void launch_gkey_out_lens(const GKeyTable& g, const uint32_t* order_slots,
   hipLaunchKernelGGL(k_gkey_out_lens, dim3(ggrid((n + 7) / 8)), dim3(GBLOCK),
                      0, s, g, order_slots, n, dts, ncols, col, lens,
                      valid_bitmap);
-  check_launchg("k_gkey_out_lens");
+  check_launch("k_gkey_out_lens");
 }
 
 __global__ void k_gkey_out_bytes(const GKeyTable g,
@@ -484,7 +479,7 @@ void launch_gkey_out_bytes(const GKeyTable& g, const uint32_t* order_slots,
                            hipStream_t s) {
   hipLaunchKernelGGL(k_gkey_out_bytes, dim3(ggrid(n)), dim3(GBLOCK), 0, s, g,
                      order_slots, n, dts, ncols, col, out_offsets, out_data);
-  check_launchg("k_gkey_out_bytes");
+  check_launch("k_gkey_out_bytes");
 }
 
 }  // namespace auron

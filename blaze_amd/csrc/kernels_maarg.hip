@@ -21,16 +21,11 @@
 
 #include "dev_agg.h"
 #include "kernels.h"
+#include "launch_check.h"
 
 namespace auron {
 
 namespace {
-inline void check_launchm(const char* name) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess)
-    throw std::runtime_error(std::string("kernel launch failed: ") + name +
-                             ": " + hipGetErrorString(e));
-}
 constexpr int MBLOCK = 256;
 constexpr int64_t MMAX_BLOCKS = 256 * 8;
 inline int mgrid(int64_t n) {
@@ -67,7 +62,7 @@ void launch_slots_upsert(const AggTable& t, const int64_t* keys,
                          uint64_t row_offset, uint32_t* slots, hipStream_t s) {
   hipLaunchKernelGGL(k_slots_upsert, dim3(mgrid(n)), dim3(MBLOCK), 0, s, t,
                      keys, key_valid, n, row_offset, slots);
-  check_launchm("k_slots_upsert");
+  check_launch("k_slots_upsert");
 }
 
 // ---- bank init -------------------------------------------------------------
@@ -89,7 +84,7 @@ void launch_ma_init(const MaDesc& d, const MaAcc& m, int64_t cap2,
                     hipStream_t s) {
   hipLaunchKernelGGL(k_ma_init, dim3(mgrid(d.n * cap2)), dim3(MBLOCK), 0, s,
                      d, m, cap2);
-  check_launchm("k_ma_init");
+  check_launch("k_ma_init");
 }
 
 // ---- per-row argument read: value in BOTH domains --------------------------
@@ -218,7 +213,7 @@ void launch_ma_update(const AggTable& t, const MaDesc& d, const MaAcc& m,
                       hipStream_t s) {
   hipLaunchKernelGGL(k_ma_update, dim3(mgrid(n)), dim3(MBLOCK), 0, s, t, d, m,
                      p, args, keys, key_valid, slots, n, row_offset);
-  check_launchm("k_ma_update");
+  check_launch("k_ma_update");
 }
 
 // ---- FIRST pass B: the winning row stores its value ------------------------
@@ -257,7 +252,7 @@ void launch_ma_first_capture(const AggTable& t, const MaDesc& d,
                              uint64_t row_offset, hipStream_t s) {
   hipLaunchKernelGGL(k_ma_first_capture, dim3(mgrid(n)), dim3(MBLOCK), 0, s,
                      t, d, m, args, slots, n, row_offset);
-  check_launchm("k_ma_first_capture");
+  check_launch("k_ma_first_capture");
 }
 
 // ---- a8 wire: freeze / parse per agg at its declared width -----------------
@@ -347,7 +342,7 @@ void launch_ma_freeze_len(const AggTable& t, const MaDesc& d, const MaAcc& m,
                           int64_t n, int32_t* lens, hipStream_t s) {
   hipLaunchKernelGGL(k_ma_freeze_len, dim3(mgrid(n)), dim3(MBLOCK), 0, s, t,
                      d, m, p, order_slots, n, lens);
-  check_launchm("k_ma_freeze_len");
+  check_launch("k_ma_freeze_len");
 }
 
 __device__ __forceinline__ uint8_t* ma_write_prim(uint8_t* q, bool valid,
@@ -439,7 +434,7 @@ void launch_ma_freeze_write(const AggTable& t, const MaDesc& d,
                             hipStream_t s) {
   hipLaunchKernelGGL(k_ma_freeze_write, dim3(mgrid(n)), dim3(MBLOCK), 0, s, t,
                      d, m, p, order_slots, n, offsets, data);
-  check_launchm("k_ma_freeze_write");
+  check_launch("k_ma_freeze_write");
 }
 
 // ---- merge frozen records (Final / PartialMerge input) ---------------------
@@ -589,7 +584,7 @@ void launch_ma_merge_frozen(const AggTable& t, const MaDesc& d,
   hipLaunchKernelGGL(k_ma_merge_frozen, dim3(mgrid(n)), dim3(MBLOCK), 0, s, t,
                      d, m, p, keys, key_valid, slots, acc_data, acc_offsets,
                      n, row_offset);
-  check_launchm("k_ma_merge_frozen");
+  check_launch("k_ma_merge_frozen");
 }
 
 // pass B over frozen records: the winning record stores its FIRST value
@@ -674,7 +669,7 @@ void launch_ma_first_capture_frozen(const AggTable& t, const MaDesc& d,
   hipLaunchKernelGGL(k_ma_first_capture_frozen, dim3(mgrid(n)), dim3(MBLOCK),
                      0, s, t, d, m, slots, acc_data, acc_offsets, n,
                      row_offset);
-  check_launchm("k_ma_first_capture_frozen");
+  check_launch("k_ma_first_capture_frozen");
 }
 
 // ---- final-output gather ---------------------------------------------------
@@ -741,7 +736,7 @@ void launch_ma_gather_out(const MaDesc& d, const MaAcc& m, int agg,
                           hipStream_t s) {
   hipLaunchKernelGGL(k_ma_gather_out, dim3(mgrid((n + 7) / 8)), dim3(MBLOCK),
                      0, s, d, m, agg, order_slots, n, values, valid_bitmap);
-  check_launchm("k_ma_gather_out");
+  check_launch("k_ma_gather_out");
 }
 
 // ---- growth ----------------------------------------------------------------
@@ -796,7 +791,7 @@ void launch_ma_rebuild(const AggTable& dst, const MaAcc& dm,
                        hipStream_t s) {
   hipLaunchKernelGGL(k_ma_rebuild, dim3(mgrid(src.cap + 2)), dim3(MBLOCK), 0,
                      s, dst, dm, src, sm, naggs);
-  check_launchm("k_ma_rebuild");
+  check_launch("k_ma_rebuild");
 }
 
 }  // namespace auron

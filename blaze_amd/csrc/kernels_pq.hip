@@ -22,16 +22,9 @@
 #include <string>
 
 #include "kernels.h"
+#include "launch_check.h"
 
 namespace auron {
-
-namespace {
-inline void check_launch_pq(const char* name) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess)
-    throw std::runtime_error(std::string(name) + ": " + hipGetErrorString(e));
-}
-}  // namespace
 
 // ---- snappy block decode, one wave per page --------------------------------
 // Tag walk is wave-uniform (every lane loads the same bytes — scalarized by
@@ -301,7 +294,7 @@ void launch_pq_pages_decode(const uint8_t* comp, const PqGpuPage* pages,
   hipLaunchKernelGGL(k_pq_pages_decode, dim3(npages), dim3(64), 0, s, comp,
                      pages, npages, scratch, valid_blob, chunks, nn_counts,
                      val_offs, err);
-  check_launch_pq("k_pq_pages_decode");
+  check_launch("k_pq_pages_decode");
 }
 
 void launch_pq_page_offsets(const PqGpuChunk* chunks, int nchunks,
@@ -309,7 +302,7 @@ void launch_pq_page_offsets(const PqGpuChunk* chunks, int nchunks,
                             uint32_t* chunk_nn, hipStream_t s) {
   hipLaunchKernelGGL(k_pq_page_offsets, dim3(nchunks), dim3(64), 0, s, chunks,
                      nchunks, nn_counts, page_dense, chunk_nn);
-  check_launch_pq("k_pq_page_offsets");
+  check_launch("k_pq_page_offsets");
 }
 
 void launch_pq_pages_compact(const PqGpuPage* pages, int npages,
@@ -321,7 +314,7 @@ void launch_pq_pages_compact(const PqGpuPage* pages, int npages,
   hipLaunchKernelGGL(k_pq_pages_compact, dim3(npages), dim3(256), 0, s, pages,
                      npages, scratch, chunks, nn_counts, val_offs, page_dense,
                      dense_blob);
-  check_launch_pq("k_pq_pages_compact");
+  check_launch("k_pq_pages_compact");
 }
 
 }  // namespace auron
