@@ -12,6 +12,7 @@
 #include <chrono>
 #include <future>
 #include <thread>
+#include <tuple>
 #include <cstring>
 #include <atomic>
 #include <map>
@@ -391,10 +392,34 @@ struct Conf {
   }
 };
 
+// Variable-width output layout: device lens[n] (int32) -> host exclusive scan
+// -> the n+1 offsets, uploaded to d_offs and returned (the caller keeps the
+// vector alive until its next sync: it is the source of the upload). Arrow
+// offsets are int32, so a total past INT32_MAX fails instead of wrapping.
+std::vector<int32_t> lens_to_offsets(const void* d_lens, int64_t n,
+                                     int32_t* d_offs, hipStream_t stream) {
+  std::vector<int32_t> offs(n + 1, 0);
+  AURON_HIP(hipMemcpyAsync(offs.data() + 1, d_lens, n * 4,
+                           hipMemcpyDeviceToHost, stream));
+  AURON_HIP(hipStreamSynchronize(stream));
+  int64_t total = 0;
+  for (int64_t i = 0; i < n; i++) {
+    total += offs[i + 1];
+    if (total > INT32_MAX)
+      FAIL("variable-width output exceeds 2 GiB in one batch (int32 offsets)");
+    offs[i + 1] = (int32_t)total;
+  }
+  AURON_HIP(hipMemcpyAsync(d_offs, offs.data(), (n + 1) * 4,
+                           hipMemcpyHostToDevice, stream));
+  return offs;
+}
+
 // ------------------------------------------------------------------ AggOp --
-// GPU AggExec: HashAgg over one Int64 grouping column with the north-star agg
-// set [SUM(Float64), COUNT] (agg_exec.rs:141-278 semantics; wider agg/type
-// coverage is tracked in DESIGN.md §scope).
+// GPU AggExec (agg_exec.rs:141-278 semantics), HashAgg in one of four modes:
+//   legacy shared-argument table — one numeric key, all aggs over one column;
+//   multi-argument bank (ma_mode_) — per-agg argument columns and pools;
+//   generalized keys (gkey_) — Utf8 / multi-column grouping tuples;
+//   two-phase fast path — partition-then-merge for large numeric-key chunks.
 class AggOp {
  public:
   AggOp(const AggNode& node, const Conf& conf, hipStream_t stream)
@@ -817,8 +842,7 @@ class AggOp {
   std::vector<OutField> key_fields() const {
     std::vector<OutField> f;
     for (size_t k = 0; k < key_cols_.size(); k++) {
-      DType kd = k < key_dts_.size() ? key_dts_[k]
-                 : (key_dt_ == DType::Unsupported ? DType::Int64 : key_dt_);
+      DType kd = k < key_dts_.size() ? key_dts_[k] : key_out_dt();
       f.push_back({key_names_[k], kd, true});
     }
     return f;
@@ -856,11 +880,126 @@ class AggOp {
     return f;
   }
 
-  // drain: produce all output batches (host-staged)
-  // Sort the COLLECT pool into {key ascending (signed), prio ascending
-  // within key} + the null-key back segment into prio order, then point the
-  // table's c_key/c_val views at the sorted arrays (binary-searched by the
-  // freeze/emit kernels). One-shot before any emit.
+  // Sort one raw COLLECT pool — keyed items at [0, n0), null-key items at
+  // [cap-n1, cap) — into the views the freeze/emit kernels binary-search:
+  // {key ascending (signed), prio ascending within key} at [0, n0) of
+  // skey/sval, then the null-key items in prio order at [n0, n0+n1) of sval.
+  // dedup (COLLECT_SET) keeps the first occurrence of each (key, value).
+  // Returns the post-dedup (n0, n1); the raw pool is left untouched.
+  std::pair<int64_t, int64_t> sort_collect_pool(
+      const long long* key, const unsigned long long* prio,
+      const unsigned long long* val, int64_t cap, int64_t n0, int64_t n1,
+      bool dedup, DevBuf& skey, DevBuf& sval) {
+    using u64 = unsigned long long;
+    if (!pinned_meta_.get()) pinned_meta_.alloc(16);
+    int64_t nmax = std::max<int64_t>(std::max(n0, n1), 1);
+    size_t tb0 = 0;
+    sort_pairs_u64_u32(nullptr, nullptr, nullptr, nullptr, nmax, nullptr,
+                       &tb0, stream_);
+    DevBuf tmp(tb0), idx(nmax * 4), idxo(nmax * 4), scr(nmax * 8);
+    skey.alloc(std::max<int64_t>(n0 + n1, 1) * 8);
+    sval.alloc(std::max<int64_t>(n0 + n1, 1) * 8);
+
+    // one stable radix pass over `by`, gathering key/prio/val (null = not
+    // carried) into the given destinations
+    auto sort_pass = [&](const u64* by, int64_t n, const u64* k, const u64* p,
+                         const u64* v, u64* k_out, u64* p_out, u64* v_out) {
+      launch_iota_u32(idx.get<uint32_t>(), n, stream_);
+      size_t tb = tmp.size();
+      sort_pairs_u64_u32(by, idx.get<uint32_t>(), scr.get<u64>(),
+                         idxo.get<uint32_t>(), n, tmp.get(), &tb, stream_);
+      if (k) launch_gather_u64_idx(k, idxo.get<uint32_t>(), n, k_out, stream_);
+      if (p) launch_gather_u64_idx(p, idxo.get<uint32_t>(), n, p_out, stream_);
+      launch_gather_u64_idx(v, idxo.get<uint32_t>(), n, v_out, stream_);
+    };
+
+    // one segment of n items into [at, at+n') of the views; seg_key is null
+    // for the null-key segment, whose key arrays stay empty throughout
+    auto sort_segment = [&](const long long* seg_key, const u64* seg_prio,
+                            const u64* seg_val, int64_t n,
+                            int64_t at) -> int64_t {
+      if (n == 0) return 0;
+      size_t kbytes = seg_key ? n * 8 : 0;
+      // working copies (ping-pong pairs)
+      DevBuf ka(kbytes), kb(kbytes), biased(kbytes), pa(n * 8), pb(n * 8),
+          va(n * 8), vb(n * 8);
+      if (seg_key)
+        AURON_HIP(hipMemcpyAsync(ka.get(), seg_key, n * 8,
+                                 hipMemcpyDeviceToDevice, stream_));
+      AURON_HIP(hipMemcpyAsync(pa.get(), seg_prio, n * 8,
+                               hipMemcpyDeviceToDevice, stream_));
+      AURON_HIP(hipMemcpyAsync(va.get(), seg_val, n * 8,
+                               hipMemcpyDeviceToDevice, stream_));
+      auto K = [](DevBuf& b) { return b.get<u64>(); };
+      auto pass = [&](DevBuf& by) {
+        sort_pass(K(by), n, K(ka), K(pa), K(va), K(kb), K(pb), K(vb));
+        std::swap(ka, kb); std::swap(pa, pb); std::swap(va, vb);
+      };
+      pass(pa);  // arrival (prio) order
+      if (dedup) {
+        // AccSet dedup (collect.rs AccSet.append: only novel values): sort
+        // by value then key (stable keeps prio asc inside runs), keep each
+        // (key, value) run head = first occurrence
+        pass(va);
+        if (seg_key) {
+          launch_bias_i64(K(ka), n, K(biased), stream_);
+          pass(biased);
+        }
+        DevBuf mark(n), pos((n + 1) * 4);
+        launch_coll_mark_heads(ka.get<long long>(), K(va), n, seg_key ? 1 : 0,
+                               mark.get<uint8_t>(), stream_);
+        size_t stb = 0;
+        scan_mask_u8(mark.get<uint8_t>(), pos.get<uint32_t>(), n, nullptr,
+                     &stb, stream_);
+        DevBuf stmp(stb);
+        scan_mask_u8(mark.get<uint8_t>(), pos.get<uint32_t>(), n, stmp.get(),
+                     &stb, stream_);
+        for (DevBuf* arr : {&ka, &pa, &va}) {
+          if (!*arr) continue;
+          launch_compact_u64(K(*arr), mark.get<uint8_t>(),
+                             pos.get<uint32_t>(), n, scr.get<u64>(), stream_);
+          AURON_HIP(hipMemcpyAsync(arr->get(), scr.get(), n * 8,
+                                   hipMemcpyDeviceToDevice, stream_));
+        }
+        // new count = scan total (slot n of pos)
+        AURON_HIP(hipMemcpyAsync(pinned_meta_.get(), pos.get<uint32_t>() + n,
+                                 4, hipMemcpyDeviceToHost, stream_));
+        AURON_HIP(hipStreamSynchronize(stream_));
+        n = (int64_t)*pinned_meta_.get<uint32_t>();
+        if (n == 0) return 0;
+        pass(pa);  // restore prio order
+      }
+      if (seg_key) {
+        // final pass: sign-biased key order, stable (prio asc within key)
+        launch_bias_i64(K(ka), n, K(biased), stream_);
+        sort_pass(K(biased), n, K(ka), nullptr, K(va), skey.get<u64>() + at,
+                  nullptr, sval.get<u64>() + at);
+      } else {
+        AURON_HIP(hipMemcpyAsync(sval.get<u64>() + at, va.get(), n * 8,
+                                 hipMemcpyDeviceToDevice, stream_));
+      }
+      AURON_HIP(hipStreamSynchronize(stream_));  // temps return to the pool
+      return n;
+    };
+
+    n0 = sort_segment(key, prio, val, n0, 0);
+    // the back segment's arrival order is reversed in memory; the prio sort
+    // restores it regardless
+    n1 = sort_segment(nullptr, prio + (cap - n1), val + (cap - n1), n1, n0);
+    return {n0, n1};
+  }
+
+  // device counters must match the sorted views' binary-search bounds
+  void upload_pool_counts(unsigned long long* d_n, int64_t n0, int64_t n1) {
+    unsigned long long* h = pinned_meta_.get<unsigned long long>();
+    h[0] = (unsigned long long)n0;
+    h[1] = (unsigned long long)n1;
+    AURON_HIP(hipMemcpyAsync(d_n, h, 16, hipMemcpyHostToDevice, stream_));
+    AURON_HIP(hipStreamSynchronize(stream_));
+  }
+
+  // Sort the legacy COLLECT pool (sort_collect_pool) and point the table's
+  // c_key/c_val views at the sorted arrays. One-shot before any emit.
   void prepare_collect() {
     if (!has_coll_ || coll_sorted_) return;
     coll_sorted_ = true;
@@ -877,328 +1016,49 @@ class AggOp {
     // approximate early trip); this is the exact post-hoc check
     if ((*errp & 4u) || n0 + n1 > coll_cap_)
       FAIL("collect pool overflow: raise AURON_HIP_COLLECT_POOL");
-    coll_n0_ = n0;
-    coll_n1_ = n1;
-    int64_t nmax = std::max<int64_t>(std::max(n0, n1), 1);
-    size_t tb0 = 0;
-    sort_pairs_u64_u32(nullptr, nullptr, nullptr, nullptr, nmax, nullptr,
-                       &tb0, stream_);
-    DevBuf tmp(tb0), idx(nmax * 4), idxo(nmax * 4), scr(nmax * 8);
-
-    // one stable radix pass over `by`, permuting key/prio/val in place
-    // (ping-pong through scratch buffers)
-    auto sort_pass = [&](unsigned long long* by, int64_t n,
-                         unsigned long long* key, unsigned long long* prio,
-                         unsigned long long* val, DevBuf& alt_key,
-                         DevBuf& alt_prio, DevBuf& alt_val) {
-      launch_iota_u32(idx.get<uint32_t>(), n, stream_);
-      size_t tb = tmp.size();
-      sort_pairs_u64_u32(by, idx.get<uint32_t>(),
-                         scr.get<unsigned long long>(), idxo.get<uint32_t>(),
-                         n, tmp.get(), &tb, stream_);
-      if (key)
-        launch_gather_u64_idx(key, idxo.get<uint32_t>(), n,
-                              alt_key.get<unsigned long long>(), stream_);
-      launch_gather_u64_idx(prio, idxo.get<uint32_t>(), n,
-                            alt_prio.get<unsigned long long>(), stream_);
-      launch_gather_u64_idx(val, idxo.get<uint32_t>(), n,
-                            alt_val.get<unsigned long long>(), stream_);
-    };
-
-    d_cskey_.alloc(std::max<int64_t>(n0, 1) * 8);
-    d_csval_.alloc(std::max<int64_t>(n0 + n1, 1) * 8);
-    if (n0 > 0) {
-      // working copies (ping-pong pairs)
-      DevBuf ka(n0 * 8), kb(n0 * 8), pa(n0 * 8), pb(n0 * 8), va(n0 * 8),
-          vb(n0 * 8), biased(n0 * 8);
-      AURON_HIP(hipMemcpyAsync(ka.get(), t_.c_key, n0 * 8,
-                               hipMemcpyDeviceToDevice, stream_));
-      AURON_HIP(hipMemcpyAsync(pa.get(), t_.c_prio, n0 * 8,
-                               hipMemcpyDeviceToDevice, stream_));
-      AURON_HIP(hipMemcpyAsync(va.get(), t_.c_val, n0 * 8,
-                               hipMemcpyDeviceToDevice, stream_));
-      auto K = [&](DevBuf& b) { return b.get<unsigned long long>(); };
-      // pass 1: prio order
-      sort_pass(K(pa), n0, K(ka), K(pa), K(va), kb, pb, vb);
-      std::swap(ka, kb); std::swap(pa, pb); std::swap(va, vb);
-      if (coll_set_) {
-        // AccSet dedup (collect.rs AccSet.append: only novel values):
-        // sort by value then key (stable keeps prio asc inside runs),
-        // keep each (key,value) run head = first occurrence
-        sort_pass(K(va), n0, K(ka), K(pa), K(va), kb, pb, vb);
-        std::swap(ka, kb); std::swap(pa, pb); std::swap(va, vb);
-        launch_bias_i64(K(ka), n0, biased.get<unsigned long long>(), stream_);
-        sort_pass(biased.get<unsigned long long>(), n0, K(ka), K(pa), K(va),
-                  kb, pb, vb);
-        std::swap(ka, kb); std::swap(pa, pb); std::swap(va, vb);
-        DevBuf mark(n0), pos((n0 + 1) * 4);
-        launch_coll_mark_heads((const long long*)K(ka), K(va), n0, 1,
-                               mark.get<uint8_t>(), stream_);
-        size_t stb = 0;
-        scan_mask_u8(mark.get<uint8_t>(), pos.get<uint32_t>(), n0, nullptr,
-                     &stb, stream_);
-        DevBuf stmp(stb);
-        scan_mask_u8(mark.get<uint8_t>(), pos.get<uint32_t>(), n0, stmp.get(),
-                     &stb, stream_);
-        for (auto arr : {&ka, &pa, &va}) {
-          launch_compact_u64(K(*arr), mark.get<uint8_t>(),
-                             pos.get<uint32_t>(), n0,
-                             scr.get<unsigned long long>(), stream_);
-          AURON_HIP(hipMemcpyAsync(arr->get(), scr.get(), n0 * 8,
-                                   hipMemcpyDeviceToDevice, stream_));
-        }
-        // new count = scan total (slot n0 of pos)
-        AURON_HIP(hipMemcpyAsync(pinned_meta_.get(),
-                                 pos.get<uint32_t>() + n0, 4,
-                                 hipMemcpyDeviceToHost, stream_));
-        AURON_HIP(hipStreamSynchronize(stream_));
-        n0 = (int64_t)*pinned_meta_.get<uint32_t>();
-        // device counter must match the binary-search bound
-        unsigned long long nn = (unsigned long long)n0;
-        AURON_HIP(hipMemcpyAsync(d_cn_.get(), &nn, 8, hipMemcpyHostToDevice,
-                                 stream_));
-        if (n0 > 0) {
-          // restore prio order for the final key pass
-          sort_pass(K(pa), n0, K(ka), K(pa), K(va), kb, pb, vb);
-          std::swap(ka, kb); std::swap(pa, pb); std::swap(va, vb);
-        }
-      }
-      if (n0 > 0) {
-        // final pass: sign-biased key order, stable (prio asc within key)
-        launch_bias_i64(K(ka), n0, biased.get<unsigned long long>(), stream_);
-        launch_iota_u32(idx.get<uint32_t>(), n0, stream_);
-        size_t tb = tmp.size();
-        sort_pairs_u64_u32(biased.get<unsigned long long>(),
-                           idx.get<uint32_t>(),
-                           scr.get<unsigned long long>(),
-                           idxo.get<uint32_t>(), n0, tmp.get(), &tb, stream_);
-        launch_gather_u64_idx(K(ka), idxo.get<uint32_t>(), n0,
-                              d_cskey_.get<unsigned long long>(), stream_);
-        launch_gather_u64_idx(K(va), idxo.get<uint32_t>(), n0,
-                              d_csval_.get<unsigned long long>(), stream_);
-      }
-      coll_n0_ = n0;
-    }
-    if (n1 > 0) {
-      // null-key back segment: prio order (+ value dedup for SET)
-      DevBuf pa(n1 * 8), pb(n1 * 8), va(n1 * 8), vb(n1 * 8);
-      AURON_HIP(hipMemcpyAsync(pa.get(), t_.c_prio + (coll_cap_ - n1), n1 * 8,
-                               hipMemcpyDeviceToDevice, stream_));
-      AURON_HIP(hipMemcpyAsync(va.get(), t_.c_val + (coll_cap_ - n1), n1 * 8,
-                               hipMemcpyDeviceToDevice, stream_));
-      auto K = [&](DevBuf& b) { return b.get<unsigned long long>(); };
-      sort_pass(K(pa), n1, nullptr, K(pa), K(va), pb, pb, vb);
-      std::swap(pa, pb); std::swap(va, vb);
-      if (coll_set_) {
-        sort_pass(K(va), n1, nullptr, K(pa), K(va), pb, pb, vb);
-        std::swap(pa, pb); std::swap(va, vb);
-        DevBuf mark(n1), pos((n1 + 1) * 4);
-        launch_coll_mark_heads(nullptr, K(va), n1, 0, mark.get<uint8_t>(),
-                               stream_);
-        size_t stb = 0;
-        scan_mask_u8(mark.get<uint8_t>(), pos.get<uint32_t>(), n1, nullptr,
-                     &stb, stream_);
-        DevBuf stmp(stb);
-        scan_mask_u8(mark.get<uint8_t>(), pos.get<uint32_t>(), n1, stmp.get(),
-                     &stb, stream_);
-        for (auto arr : {&pa, &va}) {
-          launch_compact_u64(K(*arr), mark.get<uint8_t>(),
-                             pos.get<uint32_t>(), n1,
-                             scr.get<unsigned long long>(), stream_);
-          AURON_HIP(hipMemcpyAsync(arr->get(), scr.get(), n1 * 8,
-                                   hipMemcpyDeviceToDevice, stream_));
-        }
-        AURON_HIP(hipMemcpyAsync(pinned_meta_.get(),
-                                 pos.get<uint32_t>() + n1, 4,
-                                 hipMemcpyDeviceToHost, stream_));
-        AURON_HIP(hipStreamSynchronize(stream_));
-        n1 = (int64_t)*pinned_meta_.get<uint32_t>();
-        unsigned long long nn = (unsigned long long)n1;
-        AURON_HIP(hipMemcpyAsync(d_cn_.get<uint8_t>() + 8, &nn, 8,
-                                 hipMemcpyHostToDevice, stream_));
-        if (n1 > 0) {
-          sort_pass(K(pa), n1, nullptr, K(pa), K(va), pb, pb, vb);
-          std::swap(pa, pb); std::swap(va, vb);
-        }
-      }
-      if (n1 > 0)
-        AURON_HIP(hipMemcpyAsync(
-            d_csval_.get<unsigned long long>() + coll_n0_, va.get(), n1 * 8,
-            hipMemcpyDeviceToDevice, stream_));
-      coll_n1_ = n1;
-    }
-    AURON_HIP(hipStreamSynchronize(stream_));  // temps return to the pool
+    std::tie(coll_n0_, coll_n1_) =
+        sort_collect_pool(t_.c_key, t_.c_prio, t_.c_val, coll_cap_, n0, n1,
+                          coll_set_, d_cskey_, d_csval_);
+    upload_pool_counts(d_cn_.get<unsigned long long>(), coll_n0_, coll_n1_);
     t_.c_key = d_cskey_.get<long long>();
     t_.c_val = d_csval_.get<unsigned long long>();
     t_.c_cap = coll_n0_ + coll_n1_;  // null segment ends the sorted view
   }
 
-  // Sort each multi-arg collect pool exactly like prepare_collect sorts the
-  // legacy pool: {key asc (signed), prio asc within key} + null-key back
-  // segment in prio order appended at [n0, n0+n1); COLLECT_SET pools dedup
-  // by (key, value) keeping first occurrence. The sorted views replace the
-  // raw pool pointers in mp_ (no further appends happen after finish) and
-  // the device counters are updated to the post-dedup counts.
+  // Sort each multi-arg collect pool like prepare_collect sorts the legacy
+  // one (COLLECT_SET pools dedup). The sorted views replace the raw pool
+  // pointers in mp_ (no further appends happen after finish) and the device
+  // counters are updated to the post-dedup counts.
   void prepare_ma_pools() {
     if (!ma_mode_ || ma_pools_sorted_) return;
     ma_pools_sorted_ = true;
-    if (pinned_meta_.size() < MA_MAX_POOLS * 16 + 16)
-      pinned_meta_.alloc(MA_MAX_POOLS * 16 + 16);
+    if (pinned_meta_.size() < MA_MAX_POOLS * 16)
+      pinned_meta_.alloc(MA_MAX_POOLS * 16);
     unsigned long long* h_n = pinned_meta_.get<unsigned long long>();
     AURON_HIP(hipMemcpyAsync(h_n, d_mp_n_.get(), MA_MAX_POOLS * 16,
                              hipMemcpyDeviceToHost, stream_));
     AURON_HIP(hipStreamSynchronize(stream_));
+    for (int p = 0; p < MA_MAX_POOLS; p++) {  // raw until the pool is sorted
+      mp_counts_[p][0] = (int64_t)h_n[2 * p];
+      mp_counts_[p][1] = (int64_t)h_n[2 * p + 1];
+    }
     for (int j = 0; j < ma_desc_.n; j++) {
       uint8_t p = ma_desc_.a[j].pool;
       if (p >= MA_MAX_POOLS) continue;
-      bool dedup = ma_desc_.a[j].kind == AGGL_CSET;
-      int64_t n0 = (int64_t)h_n[2 * p], n1 = (int64_t)h_n[2 * p + 1];
+      int64_t n0 = mp_counts_[p][0], n1 = mp_counts_[p][1];
       if (n0 + n1 > mp_.cap) FAIL("collect pool overflow (ma mode)");
-      int64_t nmax = std::max<int64_t>(std::max(n0, n1), 1);
-      size_t tb0 = 0;
-      sort_pairs_u64_u32(nullptr, nullptr, nullptr, nullptr, nmax, nullptr,
-                         &tb0, stream_);
-      DevBuf tmp(tb0), idx(nmax * 4), idxo(nmax * 4), scr(nmax * 8);
-      auto sort_pass = [&](unsigned long long* by, int64_t n,
-                           unsigned long long* key, unsigned long long* prio,
-                           unsigned long long* val, DevBuf& ak, DevBuf& ap,
-                           DevBuf& av) {
-        launch_iota_u32(idx.get<uint32_t>(), n, stream_);
-        size_t tb = tmp.size();
-        sort_pairs_u64_u32(by, idx.get<uint32_t>(),
-                           scr.get<unsigned long long>(),
-                           idxo.get<uint32_t>(), n, tmp.get(), &tb, stream_);
-        if (key)
-          launch_gather_u64_idx(key, idxo.get<uint32_t>(), n,
-                                ak.get<unsigned long long>(), stream_);
-        launch_gather_u64_idx(prio, idxo.get<uint32_t>(), n,
-                              ap.get<unsigned long long>(), stream_);
-        launch_gather_u64_idx(val, idxo.get<uint32_t>(), n,
-                              av.get<unsigned long long>(), stream_);
-      };
-      d_mp_skey_[p].alloc(std::max<int64_t>(n0 + n1, 1) * 8);
-      d_mp_sval_[p].alloc(std::max<int64_t>(n0 + n1, 1) * 8);
-      auto K = [&](DevBuf& bb) { return bb.get<unsigned long long>(); };
-      if (n0 > 0) {
-        DevBuf ka(n0 * 8), kb(n0 * 8), pa(n0 * 8), pb(n0 * 8), va(n0 * 8),
-            vb(n0 * 8), biased(n0 * 8);
-        AURON_HIP(hipMemcpyAsync(ka.get(), mp_.key[p], n0 * 8,
-                                 hipMemcpyDeviceToDevice, stream_));
-        AURON_HIP(hipMemcpyAsync(pa.get(), mp_.prio[p], n0 * 8,
-                                 hipMemcpyDeviceToDevice, stream_));
-        AURON_HIP(hipMemcpyAsync(va.get(), mp_.val[p], n0 * 8,
-                                 hipMemcpyDeviceToDevice, stream_));
-        sort_pass(K(pa), n0, K(ka), K(pa), K(va), kb, pb, vb);
-        std::swap(ka, kb); std::swap(pa, pb); std::swap(va, vb);
-        if (dedup) {
-          sort_pass(K(va), n0, K(ka), K(pa), K(va), kb, pb, vb);
-          std::swap(ka, kb); std::swap(pa, pb); std::swap(va, vb);
-          launch_bias_i64(K(ka), n0, biased.get<unsigned long long>(),
-                          stream_);
-          sort_pass(biased.get<unsigned long long>(), n0, K(ka), K(pa),
-                    K(va), kb, pb, vb);
-          std::swap(ka, kb); std::swap(pa, pb); std::swap(va, vb);
-          DevBuf mark(n0), pos2((n0 + 1) * 4);
-          launch_coll_mark_heads((const long long*)K(ka), K(va), n0, 1,
-                                 mark.get<uint8_t>(), stream_);
-          size_t stb = 0;
-          scan_mask_u8(mark.get<uint8_t>(), pos2.get<uint32_t>(), n0,
-                       nullptr, &stb, stream_);
-          DevBuf stmp(stb);
-          scan_mask_u8(mark.get<uint8_t>(), pos2.get<uint32_t>(), n0,
-                       stmp.get(), &stb, stream_);
-          for (auto arr : {&ka, &pa, &va}) {
-            launch_compact_u64(K(*arr), mark.get<uint8_t>(),
-                               pos2.get<uint32_t>(), n0,
-                               scr.get<unsigned long long>(), stream_);
-            AURON_HIP(hipMemcpyAsync(arr->get(), scr.get(), n0 * 8,
-                                     hipMemcpyDeviceToDevice, stream_));
-          }
-          uint32_t* hc = (uint32_t*)(h_n + MA_MAX_POOLS * 2);
-          AURON_HIP(hipMemcpyAsync(hc, pos2.get<uint32_t>() + n0, 4,
-                                   hipMemcpyDeviceToHost, stream_));
-          AURON_HIP(hipStreamSynchronize(stream_));
-          n0 = (int64_t)*hc;
-          if (n0 > 0) {  // restore prio order for the final key pass
-            sort_pass(K(pa), n0, K(ka), K(pa), K(va), kb, pb, vb);
-            std::swap(ka, kb); std::swap(pa, pb); std::swap(va, vb);
-          }
-        }
-        if (n0 > 0) {
-          launch_bias_i64(K(ka), n0, biased.get<unsigned long long>(),
-                          stream_);
-          launch_iota_u32(idx.get<uint32_t>(), n0, stream_);
-          size_t tb = tmp.size();
-          sort_pairs_u64_u32(biased.get<unsigned long long>(),
-                             idx.get<uint32_t>(),
-                             scr.get<unsigned long long>(),
-                             idxo.get<uint32_t>(), n0, tmp.get(), &tb,
-                             stream_);
-          launch_gather_u64_idx(K(ka), idxo.get<uint32_t>(), n0,
-                                d_mp_skey_[p].get<unsigned long long>(),
-                                stream_);
-          launch_gather_u64_idx(K(va), idxo.get<uint32_t>(), n0,
-                                d_mp_sval_[p].get<unsigned long long>(),
-                                stream_);
-        }
-      }
-      if (n1 > 0) {  // null-key back segment -> [n0, n0+n1) of the view
-        DevBuf pa(n1 * 8), pb(n1 * 8), va(n1 * 8), vb(n1 * 8);
-        // back segment occupies [cap-n1, cap); arrival order is reversed in
-        // memory but the prio sort below restores it regardless
-        AURON_HIP(hipMemcpyAsync(pa.get(), mp_.prio[p] + (mp_.cap - n1),
-                                 n1 * 8, hipMemcpyDeviceToDevice, stream_));
-        AURON_HIP(hipMemcpyAsync(va.get(), mp_.val[p] + (mp_.cap - n1),
-                                 n1 * 8, hipMemcpyDeviceToDevice, stream_));
-        sort_pass(K(pa), n1, nullptr, K(pa), K(va), pb, pb, vb);
-        std::swap(pa, pb); std::swap(va, vb);
-        if (dedup) {
-          sort_pass(K(va), n1, nullptr, K(pa), K(va), pb, pb, vb);
-          std::swap(pa, pb); std::swap(va, vb);
-          DevBuf mark(n1), pos2((n1 + 1) * 4);
-          launch_coll_mark_heads(nullptr, K(va), n1, 0, mark.get<uint8_t>(),
-                                 stream_);
-          size_t stb = 0;
-          scan_mask_u8(mark.get<uint8_t>(), pos2.get<uint32_t>(), n1,
-                       nullptr, &stb, stream_);
-          DevBuf stmp(stb);
-          scan_mask_u8(mark.get<uint8_t>(), pos2.get<uint32_t>(), n1,
-                       stmp.get(), &stb, stream_);
-          for (auto arr : {&pa, &va}) {
-            launch_compact_u64(K(*arr), mark.get<uint8_t>(),
-                               pos2.get<uint32_t>(), n1,
-                               scr.get<unsigned long long>(), stream_);
-            AURON_HIP(hipMemcpyAsync(arr->get(), scr.get(), n1 * 8,
-                                     hipMemcpyDeviceToDevice, stream_));
-          }
-          uint32_t* hc = (uint32_t*)(h_n + MA_MAX_POOLS * 2);
-          AURON_HIP(hipMemcpyAsync(hc, pos2.get<uint32_t>() + n1, 4,
-                                   hipMemcpyDeviceToHost, stream_));
-          AURON_HIP(hipStreamSynchronize(stream_));
-          n1 = (int64_t)*hc;
-          if (n1 > 0) {
-            sort_pass(K(pa), n1, nullptr, K(pa), K(va), pb, pb, vb);
-            std::swap(pa, pb); std::swap(va, vb);
-          }
-        }
-        if (n1 > 0)
-          AURON_HIP(hipMemcpyAsync(
-              d_mp_sval_[p].get<unsigned long long>() + n0, va.get(), n1 * 8,
-              hipMemcpyDeviceToDevice, stream_));
-      }
-      AURON_HIP(hipStreamSynchronize(stream_));  // temps return to the pool
+      std::tie(n0, n1) = sort_collect_pool(
+          mp_.key[p], mp_.prio[p], mp_.val[p], mp_.cap, n0, n1,
+          ma_desc_.a[j].kind == AGGL_CSET, d_mp_skey_[p], d_mp_sval_[p]);
+      upload_pool_counts(d_mp_n_.get<unsigned long long>() + 2 * p, n0, n1);
       mp_.key[p] = d_mp_skey_[p].get<long long>();
       mp_.val[p] = d_mp_sval_[p].get<unsigned long long>();
       mp_counts_[p][0] = n0;
       mp_counts_[p][1] = n1;
-      unsigned long long nn[2] = {(unsigned long long)n0,
-                                  (unsigned long long)n1};
-      AURON_HIP(hipMemcpyAsync(d_mp_n_.get<unsigned long long>() + 2 * p, nn,
-                               16, hipMemcpyHostToDevice, stream_));
     }
-    AURON_HIP(hipStreamSynchronize(stream_));
   }
 
+  // drain: produce all output batches (host-staged)
   std::vector<std::pair<int64_t, std::vector<HostOutCol>>> finish() {
     std::vector<std::pair<int64_t, std::vector<HostOutCol>>> out;
     drain_timing();
@@ -1303,20 +1163,15 @@ class AggOp {
     std::vector<DevOutCol> cols(2);
     DevOutCol& kc = cols[0];
     DevOutCol& bc = cols[1];
-    kc.dt = key_dt_ == DType::Unsupported ? DType::Int64 : key_dt_;
-    DevBuf keys(n * 8), sums(n * 8), svalid(bm), cnts(n * 8);
+    kc.dt = key_out_dt();
+    DevBuf keys(n * 8), wide, sums(n * 8), svalid(bm), cnts(n * 8);
     kc.validity.alloc(bm);
     launch_agg_gather_out(t_, order_slots, n, keys.get<int64_t>(),
                           kc.validity.get<uint8_t>(), sums.get<double>(),
                           svalid.get<uint8_t>(), cnts.get<long long>(),
                           nullptr, nullptr, nullptr, nullptr, stream_);
-    if (kc.dt == DType::Int32) {
-      kc.values.alloc(n * 4);
-      launch_narrow_i64_i32(keys.get<int64_t>(), n, kc.values.get<int32_t>(),
-                            stream_);
-    } else {
-      kc.values = std::move(keys);
-    }
+    narrow_keys(keys, wide, n);
+    kc.values = std::move(keys);
     // freeze lens -> device exclusive scan -> offsets (+ total in slot n)
     bc.dt = DType::Binary;
     DevBuf lens((n + 1) * 4);
@@ -1874,44 +1729,26 @@ class AggOp {
     int64_t n = (int64_t)main_order.size();
     specials_count_ = ng - n;
     if (n > 0) {
-      DevBuf d_order(n * 4), keys(n * 8), lens(n * 4), offs((n + 1) * 4);
+      DevBuf d_order(n * 4), keys(n * 8);
       AURON_HIP(hipMemcpyAsync(d_order.get(), main_order.data(), n * 4,
                                hipMemcpyHostToDevice, stream_));
       launch_agg_gather_out(t_, d_order.get<uint32_t>(), n,
                             keys.get<int64_t>(), nullptr, nullptr, nullptr,
                             nullptr, nullptr, nullptr, nullptr, nullptr,
                             stream_);
-      launch_agg_freeze_len(t_, d_order.get<uint32_t>(), n, lens.get<int32_t>(),
-                            layout_, stream_);
-      std::vector<int32_t> h_lens(n);
       std::vector<int64_t> h_keys(n);
-      AURON_HIP(hipMemcpyAsync(h_lens.data(), lens.get(), n * 4,
-                               hipMemcpyDeviceToHost, stream_));
       AURON_HIP(hipMemcpyAsync(h_keys.data(), keys.get(), n * 8,
                                hipMemcpyDeviceToHost, stream_));
-      AURON_HIP(hipStreamSynchronize(stream_));
-      std::vector<int32_t> h_offs(n + 1, 0);
-      for (int64_t i = 0; i < n; i++) h_offs[i + 1] = h_offs[i] + h_lens[i];
-      AURON_HIP(hipMemcpyAsync(offs.get(), h_offs.data(), (n + 1) * 4,
-                               hipMemcpyHostToDevice, stream_));
-      DevBuf data(h_offs[n] ? h_offs[n] : 1);
-      launch_agg_freeze_write(t_, d_order.get<uint32_t>(), n,
-                              offs.get<int32_t>(), data.get<uint8_t>(), layout_,
-                              stream_);
-      std::vector<uint8_t> h_data(h_offs[n]);
-      if (h_offs[n])
-        AURON_HIP(hipMemcpyAsync(h_data.data(), data.get(), h_offs[n],
-                                 hipMemcpyDeviceToHost, stream_));
-      AURON_HIP(hipStreamSynchronize(stream_));
+      HostOutCol rec = freeze_agg_buf(d_order.get<uint32_t>(), n);  // syncs
       if (spill_.empty()) spill_.resize(num_spill_buckets_);
       for (int64_t i = 0; i < n; i++) {
         SpillBucket& b =
             spill_[host_mix64((uint64_t)h_keys[i]) % num_spill_buckets_];
         b.keys.push_back(h_keys[i]);
         b.first_rows.push_back(main_first[i]);
-        b.lens.push_back(h_lens[i]);
-        b.data.insert(b.data.end(), h_data.begin() + h_offs[i],
-                      h_data.begin() + h_offs[i + 1]);
+        b.lens.push_back(rec.offsets[i + 1] - rec.offsets[i]);
+        b.data.insert(b.data.end(), rec.values.begin() + rec.offsets[i],
+                      rec.values.begin() + rec.offsets[i + 1]);
       }
       spill_count_++;
     }
@@ -2062,13 +1899,93 @@ class AggOp {
 
   // D2H through a reusable pinned staging buffer (pageable D2H costs ms on
   // this stack); dst vector is filled from the pinned copy
-  void d2h_pinned(void* dev, std::vector<uint8_t>* dst, size_t len) {
+  void d2h_pinned(const void* dev, std::vector<uint8_t>* dst, size_t len) {
     if (pinned_emit_.size() < len) pinned_emit_.alloc(len);
     AURON_HIP(hipMemcpyAsync(pinned_emit_.get(), dev, len,
                              hipMemcpyDeviceToHost, stream_));
     AURON_HIP(hipStreamSynchronize(stream_));
     dst->resize(len);
     memcpy(dst->data(), pinned_emit_.get(), len);
+  }
+
+  // validity bitmap of n rows to the host (synced)
+  std::vector<uint8_t> d2h_bitmap(const void* dev, int64_t n) {
+    std::vector<uint8_t> bm((n + 7) / 8);
+    AURON_HIP(hipMemcpyAsync(bm.data(), dev, bm.size(), hipMemcpyDeviceToHost,
+                             stream_));
+    AURON_HIP(hipStreamSynchronize(stream_));
+    return bm;
+  }
+
+  // Variable-width (Binary) column of n rows from a pair of kernels:
+  // write_lens(int32_t* lens) sizes each row, write_bytes(const int32_t* offs,
+  // uint8_t* data) fills the rows at the scanned offsets.
+  template <class LensFn, class BytesFn>
+  HostOutCol freeze_binary_col(int64_t n, LensFn write_lens,
+                               BytesFn write_bytes) {
+    HostOutCol col;
+    col.dt = DType::Binary;
+    DevBuf lens(n * 4), offs((n + 1) * 4);
+    write_lens(lens.get<int32_t>());
+    col.offsets = lens_to_offsets(lens.get(), n, offs.get<int32_t>(), stream_);
+    size_t total = (size_t)col.offsets[n];
+    DevBuf data(total ? total : 1);
+    write_bytes(offs.get<int32_t>(), data.get<uint8_t>());
+    d2h_pinned(data.get(), &col.values, total);
+    return col;
+  }
+
+  // the legacy table's a8 partial agg-buf column for the ordered groups
+  HostOutCol freeze_agg_buf(const uint32_t* order_slots, int64_t n) {
+    return freeze_binary_col(
+        n,
+        [&](int32_t* lens) {
+          launch_agg_freeze_len(t_, order_slots, n, lens, layout_, stream_);
+        },
+        [&](const int32_t* offs, uint8_t* data) {
+          launch_agg_freeze_write(t_, order_slots, n, offs, data, layout_,
+                                  stream_);
+        });
+  }
+
+  // COLLECT list column for the ordered groups, read through an AggTable
+  // view `tv` of a sorted pool; item_dt Int32 narrows the 8-byte pool items
+  HostOutCol coll_list_col(const AggTable& tv, const uint32_t* order_slots,
+                           int64_t n, DType item_dt) {
+    HostOutCol col;
+    col.dt = item_dt;
+    col.is_list = true;
+    DevBuf cnts(n * 4), d_off((n + 1) * 4);
+    launch_coll_counts(tv, order_slots, n, cnts.get<int32_t>(), stream_);
+    col.offsets = lens_to_offsets(cnts.get(), n, d_off.get<int32_t>(), stream_);
+    int64_t m = col.offsets[n];
+    DevBuf items(m * 8 + 8);
+    launch_coll_gather(tv, order_slots, n, d_off.get<int32_t>(),
+                       items.get<unsigned long long>(), stream_);
+    if (item_dt == DType::Int32) {
+      DevBuf narrow(m * 4 + 4);
+      launch_narrow_i64_i32(items.get<int64_t>(), m, narrow.get<int32_t>(),
+                            stream_);
+      d2h_pinned(narrow.get(), &col.values, (size_t)m * 4);
+    } else {
+      d2h_pinned(items.get(), &col.values, (size_t)m * 8);
+    }
+    return col;
+  }
+
+  DType key_out_dt() const {
+    return key_dt_ == DType::Unsupported ? DType::Int64 : key_dt_;
+  }
+
+  // Int32 keys sit widened in the i64 slots: narrow the gathered `keys` back
+  // to the declared type. The narrowed buffer replaces `keys`; the i64 one
+  // moves to `wide`, which the launch still reads until the caller syncs.
+  void narrow_keys(DevBuf& keys, DevBuf& wide, int64_t n) {
+    if (key_out_dt() != DType::Int32) return;
+    wide = std::move(keys);
+    keys.alloc(n * 4);
+    launch_narrow_i64_i32(wide.get<int64_t>(), n, keys.get<int32_t>(),
+                          stream_);
   }
 
   // decode the generalized-key grouping columns for the ordered groups
@@ -2078,31 +1995,25 @@ class AggOp {
     size_t bm = (n + 7) / 8;
     for (size_t k = 0; k < key_cols_.size(); k++) {
       HostOutCol c;
-      c.dt = key_dts_[k];
+      DType dt = key_dts_[k];
       DevBuf bmbuf(bm);
-      if (c.dt == DType::Utf8 || c.dt == DType::Binary) {
-        DevBuf lens(n * 4);
-        launch_gkey_out_lens(g_, order_slots, n, d_gkdts_.get<uint8_t>(),
-                             (int)key_cols_.size(), (int)k,
-                             lens.get<uint32_t>(), bmbuf.get<uint8_t>(),
-                             stream_);
-        std::vector<uint32_t> h_lens(n);
-        AURON_HIP(hipMemcpyAsync(h_lens.data(), lens.get(), n * 4,
-                                 hipMemcpyDeviceToHost, stream_));
-        AURON_HIP(hipStreamSynchronize(stream_));
-        c.offsets.assign(n + 1, 0);
-        for (int64_t i = 0; i < n; i++)
-          c.offsets[i + 1] = c.offsets[i] + (int32_t)h_lens[i];
-        DevBuf d_off((n + 1) * 4), data(c.offsets[n] ? c.offsets[n] : 1);
-        AURON_HIP(hipMemcpyAsync(d_off.get(), c.offsets.data(), (n + 1) * 4,
-                                 hipMemcpyHostToDevice, stream_));
-        launch_gkey_out_bytes(g_, order_slots, n, d_gkdts_.get<uint8_t>(),
-                              (int)key_cols_.size(), (int)k,
-                              d_off.get<int32_t>(), data.get<uint8_t>(),
-                              stream_);
-        d2h_pinned(data.get(), &c.values, c.offsets[n]);
+      if (dt == DType::Utf8 || dt == DType::Binary) {
+        c = freeze_binary_col(
+            n,
+            [&](int32_t* lens) {
+              launch_gkey_out_lens(g_, order_slots, n, d_gkdts_.get<uint8_t>(),
+                                   (int)key_cols_.size(), (int)k,
+                                   (uint32_t*)lens, bmbuf.get<uint8_t>(),
+                                   stream_);
+            },
+            [&](const int32_t* offs, uint8_t* data) {
+              launch_gkey_out_bytes(g_, order_slots, n,
+                                    d_gkdts_.get<uint8_t>(),
+                                    (int)key_cols_.size(), (int)k, offs, data,
+                                    stream_);
+            });
       } else {
-        size_t w = dtype_width(c.dt);
+        size_t w = dtype_width(dt);
         DevBuf vals(n * w);
         launch_gkey_out_fixed(g_, order_slots, n, d_gkdts_.get<uint8_t>(),
                               (int)key_cols_.size(), (int)k,
@@ -2110,11 +2021,8 @@ class AggOp {
                               stream_);
         d2h_pinned(vals.get(), &c.values, n * w);
       }
-      std::vector<uint8_t> h_bm(bm);
-      AURON_HIP(hipMemcpyAsync(h_bm.data(), bmbuf.get(), bm,
-                               hipMemcpyDeviceToHost, stream_));
-      AURON_HIP(hipStreamSynchronize(stream_));
-      attach_validity(&c, h_bm, n);
+      c.dt = dt;
+      attach_validity(&c, d2h_bitmap(bmbuf.get(), n), n);
       out.push_back(std::move(c));
     }
     return out;
@@ -2129,31 +2037,20 @@ class AggOp {
     size_t bm = (n + 7) / 8;
     if (!final_output_) {
       // partial: ONE Binary agg-buf column with the per-agg wire
-      DevBuf lens(n * 4), offs((n + 1) * 4);
-      launch_ma_freeze_len(t_, ma_desc_, ma_, mp_, order_slots, n,
-                           lens.get<int32_t>(), stream_);
-      std::vector<int32_t> h_lens(n);
-      AURON_HIP(hipMemcpyAsync(h_lens.data(), lens.get(), n * 4,
-                               hipMemcpyDeviceToHost, stream_));
-      AURON_HIP(hipStreamSynchronize(stream_));
-      std::vector<int32_t> h_offs(n + 1, 0);
-      for (int64_t i = 0; i < n; i++) h_offs[i + 1] = h_offs[i] + h_lens[i];
-      AURON_HIP(hipMemcpyAsync(offs.get(), h_offs.data(), (n + 1) * 4,
-                               hipMemcpyHostToDevice, stream_));
-      DevBuf data(h_offs[n] ? h_offs[n] : 1);
-      launch_ma_freeze_write(t_, ma_desc_, ma_, mp_, order_slots, n,
-                             offs.get<int32_t>(), data.get<uint8_t>(),
-                             stream_);
-      HostOutCol buf_col;
-      buf_col.dt = DType::Binary;
-      buf_col.offsets = std::move(h_offs);
-      d2h_pinned(data.get(), &buf_col.values, (size_t)buf_col.offsets[n]);
-      cols->push_back(std::move(buf_col));
+      cols->push_back(freeze_binary_col(
+          n,
+          [&](int32_t* lens) {
+            launch_ma_freeze_len(t_, ma_desc_, ma_, mp_, order_slots, n, lens,
+                                 stream_);
+          },
+          [&](const int32_t* offs, uint8_t* data) {
+            launch_ma_freeze_write(t_, ma_desc_, ma_, mp_, order_slots, n,
+                                   offs, data, stream_);
+          }));
       return;
     }
     for (int j = 0; j < ma_desc_.n; j++) {
       const MaAgg& ag = ma_desc_.a[j];
-      HostOutCol ac;
       if (ag.kind == AGGL_CLIST || ag.kind == AGGL_CSET) {
         // re-aim the legacy collect view at this pool's sorted arrays
         AggTable tv = t_;
@@ -2162,35 +2059,10 @@ class AggOp {
         tv.c_val = mp_.val[p];
         tv.c_n = d_mp_n_.get<unsigned long long>() + 2 * p;
         tv.c_cap = mp_counts_[p][0] + mp_counts_[p][1];
-        DevBuf ccnt(n * 4);
-        launch_coll_counts(tv, order_slots, n, ccnt.get<int32_t>(), stream_);
-        std::vector<int32_t> h_cnts(n);
-        AURON_HIP(hipMemcpyAsync(h_cnts.data(), ccnt.get(), n * 4,
-                                 hipMemcpyDeviceToHost, stream_));
-        AURON_HIP(hipStreamSynchronize(stream_));
-        ac.offsets.assign(n + 1, 0);
-        for (int64_t i = 0; i < n; i++)
-          ac.offsets[i + 1] = ac.offsets[i] + h_cnts[i];
-        DevBuf d_off((n + 1) * 4),
-            items((int64_t)ac.offsets[n] * 8 + 8);
-        AURON_HIP(hipMemcpyAsync(d_off.get(), ac.offsets.data(),
-                                 (n + 1) * 4, hipMemcpyHostToDevice,
-                                 stream_));
-        launch_coll_gather(tv, order_slots, n, d_off.get<int32_t>(),
-                           items.get<unsigned long long>(), stream_);
-        ac.dt = ma_out_dt(j);
-        ac.is_list = true;
-        if (ac.dt == DType::Int32) {
-          DevBuf narrow((int64_t)ac.offsets[n] * 4 + 4);
-          launch_narrow_i64_i32(items.get<int64_t>(), ac.offsets[n],
-                                narrow.get<int32_t>(), stream_);
-          d2h_pinned(narrow.get(), &ac.values, (size_t)ac.offsets[n] * 4);
-        } else {
-          d2h_pinned(items.get(), &ac.values, (size_t)ac.offsets[n] * 8);
-        }
-        cols->push_back(std::move(ac));
+        cols->push_back(coll_list_col(tv, order_slots, n, ma_out_dt(j)));
         continue;
       }
+      HostOutCol ac;
       int w = (ag.kind == AGGL_CNT) ? 8 : (ag.acc_t == 2 ? 4 : 8);
       DevBuf vals(n * w), bmbuf(bm);
       launch_ma_gather_out(ma_desc_, ma_, j, order_slots, n,
@@ -2200,11 +2072,8 @@ class AggOp {
               : (ag.kind == AGGL_AVG) ? DType::Float64
                                       : ma_out_dt(j);
       d2h_pinned(vals.get(), &ac.values, (size_t)n * w);
-      std::vector<uint8_t> h_bm(bm);
-      AURON_HIP(hipMemcpyAsync(h_bm.data(), bmbuf.get(), bm,
-                               hipMemcpyDeviceToHost, stream_));
-      AURON_HIP(hipStreamSynchronize(stream_));
-      if (ag.kind != AGGL_CNT) attach_validity(&ac, h_bm, n);
+      if (ag.kind != AGGL_CNT)
+        attach_validity(&ac, d2h_bitmap(bmbuf.get(), n), n);
       cols->push_back(std::move(ac));
     }
   }
@@ -2228,21 +2097,12 @@ class AggOp {
                           mins.get<double>(), mvalid.get<uint8_t>(),
                           maxs.get<double>(), xvalid.get<uint8_t>(), stream_);
     HostOutCol key_col;
-    key_col.dt = key_dt_ == DType::Unsupported ? DType::Int64 : key_dt_;
-    if (key_col.dt == DType::Int32) {
-      DevBuf k32(n * 4);
-      launch_narrow_i64_i32(keys.get<int64_t>(), n, k32.get<int32_t>(),
-                            stream_);
-      d2h_pinned(k32.get(), &key_col.values, n * 4);
-    } else {
-      d2h_pinned(keys.get(), &key_col.values, n * 8);
-    }
+    key_col.dt = key_out_dt();
+    DevBuf wide;
+    narrow_keys(keys, wide, n);
+    d2h_pinned(keys.get(), &key_col.values, n * dtype_width(key_col.dt));
     if (ma_mode_) {
-      std::vector<uint8_t> kvh(bm);
-      AURON_HIP(hipMemcpyAsync(kvh.data(), kvalid.get(), bm,
-                               hipMemcpyDeviceToHost, stream_));
-      AURON_HIP(hipStreamSynchronize(stream_));
-      attach_validity(&key_col, kvh, n);
+      attach_validity(&key_col, d2h_bitmap(kvalid.get(), n), n);
       cols.push_back(std::move(key_col));
       emit_ma_aggs(order_slots, n, &cols);
       return {n, std::move(cols)};
@@ -2274,39 +2134,17 @@ class AggOp {
         AURON_HIP(hipMemcpyAsync(xv.data(), xvalid.get(), bm,
                                  hipMemcpyDeviceToHost, stream_));
       }
-      std::vector<int32_t> h_coff;
-      std::vector<uint8_t> h_citems;
-      bool need_coll = false;
-      for (uint32_t k : agg_kinds_)
-        need_coll |= (k == AGGL_CLIST || k == AGGL_CSET);
-      if (need_coll) {
-        DevBuf cnts(n * 4);
-        launch_coll_counts(t_, order_slots, n, cnts.get<int32_t>(), stream_);
-        std::vector<int32_t> h_cnts(n);
-        AURON_HIP(hipMemcpyAsync(h_cnts.data(), cnts.get(), n * 4,
-                                 hipMemcpyDeviceToHost, stream_));
-        AURON_HIP(hipStreamSynchronize(stream_));
-        h_coff.assign(n + 1, 0);
-        for (int64_t i = 0; i < n; i++) h_coff[i + 1] = h_coff[i] + h_cnts[i];
-        DevBuf d_off((n + 1) * 4), items((int64_t)h_coff[n] * 8 + 8);
-        AURON_HIP(hipMemcpyAsync(d_off.get(), h_coff.data(), (n + 1) * 4,
-                                 hipMemcpyHostToDevice, stream_));
-        launch_coll_gather(t_, order_slots, n, d_off.get<int32_t>(),
-                           items.get<unsigned long long>(), stream_);
-        d2h_pinned(items.get(), &h_citems, (size_t)h_coff[n] * 8);
-      }
-      std::vector<uint8_t> h_firsts[2];
-      std::vector<uint8_t> fv[2] = {std::vector<uint8_t>(bm),
-                                    std::vector<uint8_t>(bm)};
+      const DType vdt = val_is_int_ ? DType::Int64 : DType::Float64;
+      HostOutCol coll_col;  // the one legacy pool serves every collect agg
+      if (has_coll_) coll_col = coll_list_col(t_, order_slots, n, vdt);
+      std::vector<uint8_t> h_firsts[2], fv[2];
       if (has_first_) {
         DevBuf fvals(n * 8), fvalid(bm);
         for (int w = 0; w < 2; w++) {
           launch_first_gather(t_, order_slots, n, w, fvals.get<double>(),
                               fvalid.get<uint8_t>(), stream_);
           d2h_pinned(fvals.get(), &h_firsts[w], n * 8);
-          AURON_HIP(hipMemcpyAsync(fv[w].data(), fvalid.get(), bm,
-                                   hipMemcpyDeviceToHost, stream_));
-          AURON_HIP(hipStreamSynchronize(stream_));
+          fv[w] = d2h_bitmap(fvalid.get(), n);
         }
       }
       AURON_HIP(hipStreamSynchronize(stream_));
@@ -2318,7 +2156,6 @@ class AggOp {
         attach_validity(&key_col, kv, n);
         cols.push_back(std::move(key_col));
       }
-      const DType vdt = val_is_int_ ? DType::Int64 : DType::Float64;
       for (uint32_t k : agg_kinds_) {
         HostOutCol ac;
         if (k == AGGL_CNT) {
@@ -2334,10 +2171,7 @@ class AggOp {
           ac.values = h_firsts[w];
           attach_validity(&ac, fv[w], n);
         } else if (k == AGGL_CLIST || k == AGGL_CSET) {
-          ac.dt = vdt;
-          ac.is_list = true;
-          ac.offsets = h_coff;
-          ac.values = h_citems;
+          ac = coll_col;
         } else if (k == AGGL_AVG) {
           ac.dt = DType::Float64;
           ac.values = h_avgs;
@@ -2350,25 +2184,7 @@ class AggOp {
         cols.push_back(std::move(ac));
       }
     } else {
-      // freeze (a8): lens → host scan → write
-      DevBuf lens(n * 4), offs((n + 1) * 4);
-      launch_agg_freeze_len(t_, order_slots, n, lens.get<int32_t>(), layout_,
-                            stream_);
-      std::vector<int32_t> h_lens(n);
-      AURON_HIP(hipMemcpyAsync(h_lens.data(), lens.get(), n * 4,
-                               hipMemcpyDeviceToHost, stream_));
-      AURON_HIP(hipStreamSynchronize(stream_));
-      std::vector<int32_t> h_offs(n + 1, 0);
-      for (int64_t i = 0; i < n; i++) h_offs[i + 1] = h_offs[i] + h_lens[i];
-      AURON_HIP(hipMemcpyAsync(offs.get(), h_offs.data(), (n + 1) * 4,
-                               hipMemcpyHostToDevice, stream_));
-      DevBuf data(h_offs[n] ? h_offs[n] : 1);
-      launch_agg_freeze_write(t_, order_slots, n, offs.get<int32_t>(),
-                              data.get<uint8_t>(), layout_, stream_);
-      HostOutCol buf_col;
-      buf_col.dt = DType::Binary;
-      buf_col.offsets = std::move(h_offs);
-      d2h_pinned(data.get(), &buf_col.values, (size_t)buf_col.offsets[n]);
+      HostOutCol buf_col = freeze_agg_buf(order_slots, n);  // a8
       DBG("agg.emit partial freeze d2h done");
       if (gkey_) {
         cols = emit_gkey_cols(order_slots, n);
@@ -2385,41 +2201,21 @@ class AggOp {
     int64_t n = b.num_rows;
     const DevColumn& key = b.cols.at(key_col_);
     const DevColumn& val = b.cols.at(val_col_);
-    DevBuf lens(n * 4), offs((n + 1) * 4);
-    launch_skip_freeze_len(val.validity, n, lens.get<int32_t>(), layout_,
-                           stream_);
-    std::vector<int32_t> h_lens(n);
-    AURON_HIP(hipMemcpyAsync(h_lens.data(), lens.get(), n * 4,
-                             hipMemcpyDeviceToHost, stream_));
-    AURON_HIP(hipStreamSynchronize(stream_));
-    std::vector<int32_t> h_offs(n + 1, 0);
-    for (int64_t i = 0; i < n; i++) h_offs[i + 1] = h_offs[i] + h_lens[i];
-    AURON_HIP(hipMemcpyAsync(offs.get(), h_offs.data(), (n + 1) * 4,
-                             hipMemcpyHostToDevice, stream_));
-    DevBuf data(h_offs[n] ? h_offs[n] : 1);
-    launch_skip_freeze_write((const double*)val.values, val.validity, n,
-                             offs.get<int32_t>(), data.get<uint8_t>(), layout_,
-                             val_is_int_ ? 1 : 0, stream_);
-    HostOutCol key_col, buf_col;
+    HostOutCol buf_col = freeze_binary_col(
+        n,
+        [&](int32_t* lens) {
+          launch_skip_freeze_len(val.validity, n, lens, layout_, stream_);
+        },
+        [&](const int32_t* offs, uint8_t* data) {
+          launch_skip_freeze_write((const double*)val.values, val.validity, n,
+                                   offs, data, layout_, val_is_int_ ? 1 : 0,
+                                   stream_);
+        });
+    HostOutCol key_col;
     key_col.dt = key.dt;
-    size_t kw = dtype_width(key.dt);
-    key_col.values.resize(n * kw);
-    AURON_HIP(hipMemcpyAsync(key_col.values.data(), key.values, n * kw,
-                             hipMemcpyDeviceToHost, stream_));
-    std::vector<uint8_t> kv;
-    if (key.validity) {
-      kv.resize((n + 7) / 8);
-      AURON_HIP(hipMemcpyAsync(kv.data(), key.validity, kv.size(),
-                               hipMemcpyDeviceToHost, stream_));
-    }
-    buf_col.dt = DType::Binary;
-    buf_col.offsets = std::move(h_offs);
-    buf_col.values.resize(buf_col.offsets[n]);
-    AURON_HIP(hipMemcpyAsync(buf_col.values.data(), data.get(),
-                             buf_col.values.size(), hipMemcpyDeviceToHost,
-                             stream_));
-    AURON_HIP(hipStreamSynchronize(stream_));
-    if (!kv.empty()) key_col.validity = std::move(kv);
+    d2h_pinned(key.values, &key_col.values, n * dtype_width(key.dt));
+    // pass-through keeps the input's bitmap as is (no null_count pruning)
+    if (key.validity) key_col.validity = d2h_bitmap(key.validity, n);
     std::vector<HostOutCol> cols;
     cols.push_back(std::move(key_col));
     cols.push_back(std::move(buf_col));
@@ -2718,16 +2514,10 @@ class ShuffleOp {
         DevBuf lens(n * 4);
         launch_gather_lens(src.offsets, perm.get<uint32_t>(), n,
                            lens.get<int32_t>(), stream_);
-        std::vector<int32_t> h_lens(n);
-        AURON_HIP(hipMemcpyAsync(h_lens.data(), lens.get(), n * 4,
-                                 hipMemcpyDeviceToHost, stream_));
-        AURON_HIP(hipStreamSynchronize(stream_));
-        h_offsets[c].assign(n + 1, 0);
-        for (int64_t i = 0; i < n; i++)
-          h_offsets[c][i + 1] = h_offsets[c][i] + h_lens[i];
-        DevBuf d_off((n + 1) * 4), d_data(h_offsets[c][n] ? h_offsets[c][n] : 1);
-        AURON_HIP(hipMemcpyAsync(d_off.get(), h_offsets[c].data(), (n + 1) * 4,
-                                 hipMemcpyHostToDevice, stream_));
+        DevBuf d_off((n + 1) * 4);
+        h_offsets[c] =
+            lens_to_offsets(lens.get(), n, d_off.get<int32_t>(), stream_);
+        DevBuf d_data(h_offsets[c][n] ? h_offsets[c][n] : 1);
         launch_gather_bytes((const uint8_t*)src.values, src.offsets,
                             perm.get<uint32_t>(), d_off.get<int32_t>(), n,
                             d_data.get<uint8_t>(), stream_);
@@ -2932,15 +2722,9 @@ class FilterOp {
     if (c.dt == DType::Binary || c.dt == DType::Utf8) {
       DevBuf lens(m * 4);
       launch_gather_lens(c.offsets, sel, m, lens.get<int32_t>(), stream_);
-      std::vector<int32_t> h_lens(m);
-      AURON_HIP(hipMemcpyAsync(h_lens.data(), lens.get(), m * 4,
-                               hipMemcpyDeviceToHost, stream_));
-      AURON_HIP(hipStreamSynchronize(stream_));
-      std::vector<int32_t> h_offs(m + 1, 0);
-      for (int64_t i = 0; i < m; i++) h_offs[i + 1] = h_offs[i] + h_lens[i];
       out.own_offsets.alloc((m + 1) * 4);
-      AURON_HIP(hipMemcpyAsync(out.own_offsets.get(), h_offs.data(),
-                               (m + 1) * 4, hipMemcpyHostToDevice, stream_));
+      std::vector<int32_t> h_offs = lens_to_offsets(
+          lens.get(), m, out.own_offsets.get<int32_t>(), stream_);
       out.offsets = out.own_offsets.get<int32_t>();
       out.data_len = h_offs[m];
       out.own_values.alloc(out.data_len ? out.data_len : 1);

@@ -261,3 +261,64 @@ def test_collect_set_spill_drain():
     assert len(got_keys) == len(ref)
     for i, k in enumerate(got_keys):
         np.testing.assert_allclose(gl[i], np.array(ref[int(k)]), rtol=1e-12)
+
+
+def test_multi_arg_collect_null_keys_and_duplicates():
+    """collect_set(a), collect_list(b), collect_set(b) over two argument
+    columns: repeated families put BOTH the Partial and the Final side in
+    multi-argument mode, so every pool goes through the multi-argument pool
+    sort — set dedup on the keyed segment and on the null-key back segment,
+    with an i64::MIN key next to the null-key group."""
+    rng = np.random.default_rng(67)
+    n = 4_000
+    keys = rng.integers(0, 40, n).astype(np.int64)
+    keys[rng.random(n) < 0.03] = np.iinfo(np.int64).min
+    kv = rng.random(n) >= 0.1
+    a = rng.integers(0, 8, n).astype(np.float64)
+    b = rng.integers(-4, 4, n).astype(np.float64)
+    av = rng.random(n) >= 0.05
+    bv = rng.random(n) >= 0.05
+    fields = [plan.field("k", plan.DT_INT64, True),
+              plan.field("a", plan.DT_FLOAT64, True),
+              plan.field("b", plan.DT_FLOAT64, True)]
+    aggs = [plan.agg_expr(plan.AGG_COLLECT_SET, [plan.column("a", 1)],
+                          plan.DT_FLOAT64),
+            plan.agg_expr(plan.AGG_COLLECT_LIST, [plan.column("b", 2)],
+                          plan.DT_FLOAT64),
+            plan.agg_expr(plan.AGG_COLLECT_SET, [plan.column("b", 2)],
+                          plan.DT_FLOAT64)]
+    names = ["set_a", "list_b", "set_b"]
+    reader = plan.ffi_reader(fields, "input0")
+    partial = plan.agg(reader, [plan.column("k", 0)], aggs,
+                       [plan.MODE_PARTIAL] * 3, ["k"], names)
+    final = plan.agg(partial, [plan.column("k", 0)], aggs,
+                     [plan.MODE_FINAL] * 3, ["k"], names)
+    step = 1_000
+    batches = [[(keys[i:i + step], kv[i:i + step]),
+                (a[i:i + step], av[i:i + step]),
+                (b[i:i + step], bv[i:i + step])]
+               for i in range(0, n, step)]
+    t = blaze_amd.Task(plan.task_definition(final), batches=batches)
+    outs = t.run()
+    t.finalize()
+    got_keys = np.concatenate([ob[0]["values"] for ob in outs])
+    got_kv = np.concatenate(
+        [ob[0]["valid"] if ob[0].get("valid") is not None
+         else np.ones(len(ob[0]["values"]), bool) for ob in outs])
+    got = [_concat_lists([ob[1 + j] for ob in outs]) for j in range(3)]
+
+    ok, set_a = oracle.collect_groups(keys, a, av, distinct=True,
+                                      key_valid=kv)
+    ok_l, list_b = oracle.collect_groups(keys, b, bv, key_valid=kv)
+    ok_s, set_b = oracle.collect_groups(keys, b, bv, distinct=True,
+                                        key_valid=kv)
+    assert ok == ok_l == ok_s
+    assert None in ok and int(np.iinfo(np.int64).min) in ok
+    exp_kv = np.array([k is not None for k in ok])
+    np.testing.assert_array_equal(got_kv, exp_kv)
+    np.testing.assert_array_equal(
+        got_keys[exp_kv], np.array([k for k in ok if k is not None]))
+    for g, e in zip(got, (set_a, list_b, set_b)):
+        assert len(g) == len(e)
+        for gi, ei in zip(g, e):
+            np.testing.assert_array_equal(gi, np.array(ei, np.float64))
