@@ -141,6 +141,65 @@ def debug_decode_plan(task_bytes: bytes) -> str:
     return buf.value.decode()
 
 
+def debug_compile_expr(task_bytes: bytes) -> str:
+    """Compile the expressions of a Filter / Projection plan on the host and
+    return the program text, or "ERROR: <cause>" as plan build would fail."""
+    L = lib()
+    L.auron_debug_compile_expr.restype = c.c_int32
+    L.auron_debug_compile_expr.argtypes = [c.c_char_p, c.c_size_t, c.c_char_p,
+                                           c.c_size_t]
+    buf = c.create_string_buffer(1 << 16)
+    rc = L.auron_debug_compile_expr(task_bytes, len(task_bytes), buf, len(buf))
+    assert rc >= 0
+    return buf.value.decode()
+
+
+_EXPR_NP = {0: np.int32, 1: np.int64, 2: np.float64, 3: np.bool_}
+
+
+def debug_eval_expr(task_bytes: bytes, cols, expr_index=0):
+    """Run one compiled expression of a Filter / Projection plan on host
+    arrays (no GPU): the interpreter shares the kernel's per-row evaluator.
+    cols: list of (values ndarray, valid bool-array-or-None), one per input
+    column. Returns (values, state) with state 0 valid / 1 null / 2 poison;
+    values are 0 (False) where state != 0."""
+    L = lib()
+    L.auron_debug_eval_expr.restype = c.c_int32
+    L.auron_debug_eval_expr.argtypes = [
+        c.c_char_p, c.c_size_t, c.c_int32, c.c_int32,
+        c.POINTER(c.c_void_p), c.POINTER(c.c_void_p), c.c_int64, c.c_void_p,
+        c.c_void_p, c.c_char_p, c.c_size_t]
+    n = len(cols[0][0]) if cols else 0
+    keep = []
+    vals = (c.c_void_p * max(len(cols), 1))()
+    valid = (c.c_void_p * max(len(cols), 1))()
+    for i, (v, m) in enumerate(cols):
+        v = np.ascontiguousarray(v)
+        assert len(v) == n
+        keep.append(v)
+        vals[i] = v.ctypes.data
+        if m is not None:
+            m = np.ascontiguousarray(np.asarray(m, dtype=bool).astype(np.uint8))
+            assert len(m) == n
+            keep.append(m)
+            valid[i] = m.ctypes.data
+    bits = np.zeros(n, dtype=np.uint64)
+    state = np.zeros(n, dtype=np.uint8)
+    err = c.create_string_buffer(1024)
+    ty = L.auron_debug_eval_expr(task_bytes, len(task_bytes), expr_index,
+                                 len(cols), vals, valid, n, bits.ctypes.data,
+                                 state.ctypes.data, err, len(err))
+    if ty < 0:
+        raise RuntimeError(err.value.decode())
+    if ty == 0:
+        out = bits.view(np.int64).astype(np.int32)
+    elif ty == 3:
+        out = bits != 0
+    else:
+        out = bits.view(_EXPR_NP[ty]).copy()
+    return out, state
+
+
 def _bitmap(valid, n):
     if valid is None:
         return None

@@ -23,7 +23,9 @@
 
 #include "../../include/auron_hip.h"
 #include "dev.h"
+#include "expr.h"
 #include "kernels.h"
+#include "kernels_expr.h"
 #include "plan.h"
 #include "ipc_scalar.h"
 #include "parquet.h"
@@ -2582,21 +2584,75 @@ class ShuffleOp {
   std::vector<DevBatch> staged_;
 };
 
+// ------------------------------------------------------------- ExprRunner --
+// Binds a compiled ExprProgram (expr.h) to the columns of one device batch
+// and launches k_expr_eval. The caller owns the error flag and reads it back
+// at its next host sync.
+struct ExprRunner {
+  ExprProgram prog;
+
+  // fills prog / vals / valid / n; returns the nullable-slot mask
+  uint32_t bind(const DevBatch& in, ExprKernArgs* a) const {
+    memset((void*)a, 0, sizeof(*a));
+    a->prog = prog;
+    a->n = in.num_rows;
+    uint32_t nullable = 0;
+    for (int s = 0; s < prog.nslots; s++) {
+      const DevColumn& c = in.cols.at(prog.slot_col[s]);
+      if (c.dt != expr_ty_dtype((ExprTy)prog.slot_ty[s]))
+        FAIL("expression input column " + std::to_string(prog.slot_col[s]) +
+             " arrived with a dtype other than the plan's");
+      if (c.len < in.num_rows) FAIL("expression input column too short");
+      a->vals[s] = c.values;
+      a->valid[s] = c.validity;
+      if (c.validity) nullable |= 1u << s;
+    }
+    return nullable;
+  }
+};
+
 // --------------------------------------------------------------- FilterOp --
 // FilterExec (filter_exec.rs:174-198): ANDed predicates -> selection mask ->
-// stable compaction. Predicate forms on the hot path: Column <op> Literal,
-// IsNotNull/IsNull(Column).
+// stable compaction. Column <op> Literal, IsNotNull/IsNull(Column) and And of
+// those run the per-predicate mask kernels; any other predicate shape turns
+// the whole predicate list into one ExprProgram evaluated in mask mode.
 class FilterOp {
  public:
-  FilterOp(const FilterNode& node, hipStream_t stream) : stream_(stream) {
-    for (const Expr& e : node.predicates) compile(e);
-    if (preds_.empty()) FAIL("FilterExec without usable predicates");
+  FilterOp(const FilterNode& node, const std::vector<DType>* in_dtypes,
+           hipStream_t stream)
+      : stream_(stream) {
+    try {
+      for (const Expr& e : node.predicates) compile(e);
+    } catch (const EngineError&) {
+      preds_.clear();
+      use_prog_ = true;
+    }
+    if (use_prog_) {
+      if (!in_dtypes)
+        FAIL("FilterExec: computed predicates need a statically typed input "
+             "(not available above an Agg)");
+      std::string err;
+      if (!compile_filter_program(node.predicates, *in_dtypes, &runner_.prog,
+                                  &err))
+        FAIL("FilterExec: " + err);
+      d_err_.alloc(4);
+      AURON_HIP(hipMemsetAsync(d_err_.get(), 0, 4, stream_));
+    } else if (preds_.empty()) {
+      FAIL("FilterExec without usable predicates");
+    }
   }
 
   DevBatch apply(DevBatch&& in) {
     int64_t n = in.num_rows;
     if (n == 0) return std::move(in);
     DevBuf mask(n);
+    if (use_prog_) {
+      ExprKernArgs a;
+      runner_.bind(in, &a);
+      a.out_mask = mask.get<uint8_t>();
+      a.error_flag = d_err_.get<uint32_t>();
+      launch_expr_eval(a, stream_);
+    }
     for (size_t pi = 0; pi < preds_.size(); pi++) {
       const Pred& p = preds_[pi];
       const DevColumn& c = in.cols.at(p.col);
@@ -2622,7 +2678,12 @@ class FilterOp {
     uint32_t* h_cnt = pinned_.get<uint32_t>();
     AURON_HIP(hipMemcpyAsync(h_cnt, positions.get<uint32_t>() + n, 4,
                              hipMemcpyDeviceToHost, stream_));
+    h_cnt[1] = 0;
+    if (use_prog_ && runner_.prog.can_poison)
+      AURON_HIP(hipMemcpyAsync(h_cnt + 1, d_err_.get(), 4,
+                               hipMemcpyDeviceToHost, stream_));
     AURON_HIP(hipStreamSynchronize(stream_));
+    if (h_cnt[1]) FAIL("Divide by zero error");
     int64_t m = *h_cnt;
     DevBatch out;
     out.num_rows = m;
@@ -2756,44 +2817,118 @@ class FilterOp {
 
   hipStream_t stream_;
   std::vector<Pred> preds_;
+  bool use_prog_ = false;
+  ExprRunner runner_;
+  DevBuf d_err_;
   DevBuf scan_tmp_;
   PinnedBuf pinned_;
   std::vector<DevBatch> held_;
 };
 
 // -------------------------------------------------------------- ProjectOp --
-// ProjectionExec (project_exec.rs): Column-only projection on this path
-// (expression evaluation breadth is out of hot-path scope and fails loudly).
+// ProjectionExec (project_exec.rs): Column exprs are zero-copy views; every
+// other expr is compiled to an ExprProgram and evaluated by k_expr_eval into
+// an owned column. Also serves as the implicit stage that computes Agg
+// grouping / argument expressions.
 class ProjectOp {
  public:
-  explicit ProjectOp(const ProjectionNode& node) {
-    for (const Expr& e : node.exprs) {
-      if (e.kind != Expr::Column)
-        FAIL("ProjectionExec: only Column exprs on the hot path");
-      cols_.push_back(e.col_index);
+  ProjectOp(const std::vector<Expr>& exprs, const std::vector<DType>* in_dtypes,
+            hipStream_t stream)
+      : stream_(stream) {
+    for (const Expr& e : exprs) {
+      Item it;
+      if (e.kind == Expr::Column) {
+        it.col = (int)e.col_index;
+        if (in_dtypes && e.col_index < in_dtypes->size())
+          it.dt = (*in_dtypes)[e.col_index];
+      } else {
+        if (!in_dtypes)
+          FAIL("ProjectionExec: computed exprs need a statically typed input "
+               "(not available above an Agg)");
+        std::string err;
+        if (!compile_value_program(e, *in_dtypes, &it.run.prog, &err))
+          FAIL("ProjectionExec: " + err);
+        it.dt = expr_ty_dtype((ExprTy)it.run.prog.root_ty);
+        any_poison_ |= it.run.prog.can_poison != 0;
+        any_computed_ = true;
+      }
+      items_.push_back(std::move(it));
     }
+    if (any_computed_) {
+      d_err_.alloc(4);
+      AURON_HIP(hipMemsetAsync(d_err_.get(), 0, 4, stream_));
+    }
+  }
+
+  // output dtypes (Unsupported where a Column's input type is not known)
+  std::vector<DType> output_dtypes() const {
+    std::vector<DType> d;
+    for (const Item& it : items_) d.push_back(it.dt);
+    return d;
   }
 
   DevBatch apply(DevBatch&& in) {
     DevBatch out;
-    out.num_rows = in.num_rows;
-    for (uint32_t ci : cols_) {
-      DevColumn& src = in.cols.at(ci);
-      DevColumn view;
-      view.dt = src.dt;
-      view.len = src.len;
-      view.values = src.values;
-      view.validity = src.validity;
-      view.offsets = src.offsets;
-      view.data_len = src.data_len;
-      out.cols.push_back(std::move(view));
+    const int64_t n = in.num_rows;
+    out.num_rows = n;
+    for (const Item& it : items_) {
+      if (it.col >= 0) {
+        DevColumn& src = in.cols.at(it.col);
+        DevColumn view;
+        view.dt = src.dt;
+        view.len = src.len;
+        view.values = src.values;
+        view.validity = src.validity;
+        view.offsets = src.offsets;
+        view.data_len = src.data_len;
+        out.cols.push_back(std::move(view));
+        continue;
+      }
+      DevColumn oc;
+      oc.dt = it.dt;
+      oc.len = n;
+      if (n > 0) {
+        ExprKernArgs a;
+        uint32_t nullable = it.run.bind(in, &a);
+        const size_t w = dtype_width(it.dt);
+        oc.own_values.alloc((size_t)n * w);
+        oc.values = oc.own_values.get();
+        a.out_vals = oc.own_values.get();
+        a.out_width = (int32_t)w;
+        if (expr_result_nullable(it.run.prog, nullable)) {
+          // whole 64-row words: one 8-byte store per wave
+          oc.own_validity.alloc((size_t)((n + 63) / 64) * 8);
+          oc.validity = oc.own_validity.get<uint8_t>();
+          a.out_valid = oc.own_validity.get<uint64_t>();
+        }
+        a.error_flag = d_err_.get<uint32_t>();
+        launch_expr_eval(a, stream_);
+      }
+      out.cols.push_back(std::move(oc));
     }
-    held_.push_back(std::move(in));  // owner of the viewed buffers
+    if (any_poison_ && n > 0) {
+      if (!pinned_.get()) pinned_.alloc(8);
+      uint32_t* h_err = pinned_.get<uint32_t>();
+      AURON_HIP(hipMemcpyAsync(h_err, d_err_.get(), 4, hipMemcpyDeviceToHost,
+                               stream_));
+      AURON_HIP(hipStreamSynchronize(stream_));
+      if (*h_err) FAIL("Divide by zero error");
+    }
+    held_.push_back(std::move(in));  // owner of the viewed / read buffers
     return out;
   }
 
  private:
-  std::vector<uint32_t> cols_;
+  struct Item {
+    int col = -1;  // >= 0: zero-copy view of that input column
+    DType dt = DType::Unsupported;
+    ExprRunner run;
+  };
+  hipStream_t stream_;
+  std::vector<Item> items_;
+  bool any_computed_ = false, any_poison_ = false;
+  DevBuf d_err_;
+  PinnedBuf pinned_;
   std::vector<DevBatch> held_;
 };
 
@@ -2813,6 +2948,7 @@ struct Runtime {
     std::unique_ptr<ProjectOp> project;
   };
   std::vector<Stage> stages_;
+  bool terminal_transform_ = false;  // last stage is a Filter / Projection
   std::vector<OutField> out_fields;
   int ipc_codec_ = 0;  // IpcReader block codec (SPARK_IO_COMPRESSION_CODEC)
   std::vector<std::pair<int64_t, std::vector<HostOutCol>>> outputs;
@@ -2864,16 +3000,61 @@ struct Runtime {
         leaf->kind != PlanNode::ParquetScan)
       FAIL("plan leaf must be FFIReader/IpcReader/ParquetScan on this path");
 
+    // static schema of the batches between stages: expression programs are
+    // type-checked against it at plan build. An Agg fixes its output types
+    // only when it sees data, so the schema is unknown above one.
+    std::vector<OutField> cur;
+    bool cur_known = true;
+    {
+      const Schema* ls = leaf->kind == PlanNode::FFIReader
+                             ? &leaf->ffi_reader->schema
+                         : leaf->kind == PlanNode::IpcReader
+                             ? &leaf->ipc_reader->schema
+                             : &leaf->parquet->schema;
+      std::vector<uint32_t> pick;
+      if (leaf->kind == PlanNode::ParquetScan) pick = leaf->parquet->projection;
+      if (pick.empty())
+        for (uint32_t i = 0; i < ls->fields.size(); i++) pick.push_back(i);
+      for (uint32_t i : pick) {
+        if (i >= ls->fields.size()) FAIL("scan projection out of range");
+        cur.push_back({ls->fields[i].name, ls->fields[i].dtype, true});
+      }
+    }
+    auto cur_dtypes = [&]() {
+      std::vector<DType> d;
+      for (const OutField& f : cur) d.push_back(f.dt);
+      return d;
+    };
+
     // middle ops (leaf-1 ... root), in execution order
     stages_.clear();
+    terminal_transform_ = false;
     for (auto it = chain.rbegin() + 1; it != chain.rend(); ++it) {
       const PlanNode* node = *it;
+      if (!stages_.empty() && stages_.back().kind == Stage::ShuffleS)
+        FAIL("operator above ShuffleWriter unsupported");
       Stage st;
+      std::vector<DType> in_dt = cur_dtypes();
+      const std::vector<DType>* in_dtp = cur_known ? &in_dt : nullptr;
       switch (node->kind) {
-        case PlanNode::Agg:
+        case PlanNode::Agg: {
           st.kind = Stage::AggS;
-          st.agg = std::make_unique<AggOp>(*node->agg, conf, stream);
+          AggNode lowered;
+          std::vector<Expr> pre;
+          if (lower_agg_inputs(*node->agg, &lowered, &pre)) {
+            // implicit projection directly in front of the Agg: referenced
+            // columns + computed grouping / argument columns
+            Stage ps;
+            ps.kind = Stage::ProjectS;
+            ps.project = std::make_unique<ProjectOp>(pre, in_dtp, stream);
+            stages_.push_back(std::move(ps));
+            st.agg = std::make_unique<AggOp>(lowered, conf, stream);
+          } else {
+            st.agg = std::make_unique<AggOp>(*node->agg, conf, stream);
+          }
+          cur_known = false;
           break;
+        }
         case PlanNode::ShuffleWriter:
           st.kind = Stage::ShuffleS;
           st.shuffle = std::make_unique<ShuffleOp>(*node->shuffle_writer, conf,
@@ -2881,18 +3062,42 @@ struct Runtime {
           break;
         case PlanNode::Filter:
           st.kind = Stage::FilterS;
-          st.filter = std::make_unique<FilterOp>(*node->filter, stream);
+          st.filter = std::make_unique<FilterOp>(*node->filter, in_dtp, stream);
           break;
-        case PlanNode::Projection:
+        case PlanNode::Projection: {
+          const ProjectionNode& pn = *node->projection;
           st.kind = Stage::ProjectS;
-          st.project = std::make_unique<ProjectOp>(*node->projection);
+          st.project = std::make_unique<ProjectOp>(pn.exprs, in_dtp, stream);
+          std::vector<DType> od = st.project->output_dtypes();
+          std::vector<OutField> next;
+          for (size_t i = 0; i < od.size(); i++)
+            next.push_back({i < pn.names.size() ? pn.names[i]
+                                                : "col" + std::to_string(i),
+                            od[i], true});
+          cur = std::move(next);
           break;
+        }
         default:
           FAIL("unsupported operator in plan chain");
       }
-      if (!stages_.empty() && stages_.back().kind == Stage::ShuffleS)
-        FAIL("operator above ShuffleWriter unsupported");
       stages_.push_back(std::move(st));
+    }
+    // A plan that ends in a Filter or Projection has no pipeline breaker to
+    // stage its output: batches leaving the chain are emitted as ordinary
+    // host task output, in input order.
+    if (!stages_.empty() && (stages_.back().kind == Stage::FilterS ||
+                             stages_.back().kind == Stage::ProjectS)) {
+      if (!cur_known)
+        FAIL("Filter/Projection above an Agg as the plan's last stage "
+             "unsupported");
+      if (conf.get_i("AURON_HIP_DEVICE_OUTPUT", 0) != 0)
+        FAIL("AURON_HIP_DEVICE_OUTPUT on a plan ending in Filter/Projection "
+             "unsupported (its output is host batches)");
+      for (const OutField& f : cur)
+        if (!dtype_format(f.dt) || f.dt == DType::Unsupported)
+          FAIL("terminal Filter/Projection: unsupported output column dtype");
+      terminal_transform_ = true;
+      out_fields = cur;
     }
 
     // pump input through the chain
@@ -2965,7 +3170,7 @@ struct Runtime {
         out_fields.clear();
       }
     }
-    if (!has_shuffle && !last_agg)
+    if (!has_shuffle && !last_agg && !terminal_transform_)
       FAIL("plan without Agg/ShuffleWriter sink unsupported");
     if (last_agg) {
       metrics["num_groups"] = (int64_t)last_agg->num_groups_host();
@@ -3579,7 +3784,100 @@ struct Runtime {
           break;
       }
     }
-    FAIL("batch fed past end of chain");
+    if (!terminal_transform_) FAIL("batch fed past end of chain");
+    emit_host(std::move(b));
+  }
+
+  // Agg inputs that are not plain Columns (Partial mode only: a merging Agg
+  // reads the accumulator column, never its argument exprs). Returns false
+  // when there is nothing to lower. Otherwise *pre is the projection list —
+  // each referenced Column once, then each computed expr — and *out is the
+  // AggNode with every grouping expr / argument rewritten to a Column of
+  // that projection. NULL-literal arguments stay as they are.
+  static bool lower_agg_inputs(const AggNode& node, AggNode* out,
+                               std::vector<Expr>* pre) {
+    if (node.modes.empty() || node.modes[0] != AggMode::Partial) return false;
+    bool any = false;
+    for (const Expr& g : node.grouping_exprs) any |= g.kind != Expr::Column;
+    for (const Expr& a : node.agg_exprs)
+      if (!a.children.empty())
+        any |= a.children[0].kind != Expr::Column &&
+               a.children[0].kind != Expr::Literal;
+    if (!any) return false;
+    out->exec_mode = node.exec_mode;
+    out->grouping_exprs = node.grouping_exprs;
+    out->agg_exprs = node.agg_exprs;
+    out->modes = node.modes;
+    out->grouping_names = node.grouping_names;
+    out->agg_names = node.agg_names;
+    out->initial_input_buffer_offset = node.initial_input_buffer_offset;
+    out->supports_partial_skipping = node.supports_partial_skipping;
+    std::map<uint32_t, uint32_t> col_at;  // input column -> projection index
+    auto rewrite = [&](Expr& e, const std::string& name) {
+      if (e.kind == Expr::Literal) return;
+      uint32_t at;
+      if (e.kind == Expr::Column) {
+        auto f = col_at.find(e.col_index);
+        if (f == col_at.end()) {
+          at = (uint32_t)pre->size();
+          col_at[e.col_index] = at;
+          pre->push_back(e);
+        } else {
+          at = f->second;
+        }
+      } else {
+        at = (uint32_t)pre->size();
+        pre->push_back(e);
+      }
+      Expr c;
+      c.kind = Expr::Column;
+      c.col_name = e.kind == Expr::Column ? e.col_name : name;
+      c.col_index = at;
+      e = std::move(c);
+    };
+    for (size_t i = 0; i < out->grouping_exprs.size(); i++)
+      rewrite(out->grouping_exprs[i], "#group" + std::to_string(i));
+    for (size_t i = 0; i < out->agg_exprs.size(); i++)
+      if (!out->agg_exprs[i].children.empty())
+        rewrite(out->agg_exprs[i].children[0], "#arg" + std::to_string(i));
+    return true;
+  }
+
+  // terminal Filter/Projection output: download one device batch into the
+  // host output queue
+  void emit_host(DevBatch&& b) {
+    const int64_t n = b.num_rows;
+    if (n == 0) return;
+    std::vector<HostOutCol> cols(b.cols.size());
+    for (size_t i = 0; i < b.cols.size(); i++) {
+      const DevColumn& c = b.cols[i];
+      HostOutCol& h = cols[i];
+      h.dt = c.dt;
+      if (c.dt == DType::Binary || c.dt == DType::Utf8) {
+        h.offsets.resize(n + 1);
+        AURON_HIP(hipMemcpyAsync(h.offsets.data(), c.offsets, (n + 1) * 4,
+                                 hipMemcpyDeviceToHost, stream));
+        h.values.resize((size_t)c.data_len);
+        if (c.data_len > 0)
+          AURON_HIP(hipMemcpyAsync(h.values.data(), c.values,
+                                   (size_t)c.data_len, hipMemcpyDeviceToHost,
+                                   stream));
+      } else {
+        const size_t w = dtype_width(c.dt);
+        if (w == 0) FAIL("terminal output: unsupported column dtype");
+        h.values.resize((size_t)n * w);
+        AURON_HIP(hipMemcpyAsync(h.values.data(), c.values, (size_t)n * w,
+                                 hipMemcpyDeviceToHost, stream));
+      }
+      if (c.validity) {
+        h.validity.resize((size_t)(n + 7) / 8);
+        AURON_HIP(hipMemcpyAsync(h.validity.data(), c.validity,
+                                 h.validity.size(), hipMemcpyDeviceToHost,
+                                 stream));
+      }
+    }
+    AURON_HIP(hipStreamSynchronize(stream));
+    outputs.emplace_back(n, std::move(cols));
   }
 
   DevBatch host_out_to_dev(const std::pair<int64_t, std::vector<HostOutCol>>& ob,
@@ -4163,9 +4461,151 @@ int32_t auron_debug_decode_plan(const uint8_t* data, size_t len, char* out,
       }
     }
   }
+  // expression trees of Filter / Projection nodes, root to leaf, appended
+  // after the chain summary
+  if (td) {
+    std::string ex;
+    const PlanNode* p = td->plan.get();
+    while (p) {
+      switch (p->kind) {
+        case PlanNode::ShuffleWriter: p = p->shuffle_writer->input.get(); break;
+        case PlanNode::Agg: p = p->agg->input.get(); break;
+        case PlanNode::Filter:
+          ex += " Filter[";
+          for (size_t i = 0; i < p->filter->predicates.size(); i++)
+            ex += (i ? "; " : "") + expr_tree_text(p->filter->predicates[i]);
+          ex += "]";
+          p = p->filter->input.get();
+          break;
+        case PlanNode::Projection:
+          ex += " Project[";
+          for (size_t i = 0; i < p->projection->exprs.size(); i++)
+            ex += (i ? "; " : "") + expr_tree_text(p->projection->exprs[i]);
+          ex += "]";
+          p = p->projection->input.get();
+          break;
+        default: p = nullptr;
+      }
+    }
+    if (!ex.empty()) s += " exprs:" + ex;
+  }
   if (s.size() + 1 > out_cap) return -1;
   memcpy(out, s.c_str(), s.size() + 1);
   return (int32_t)s.size();
+}
+
+namespace auron {
+namespace {
+// Programs of a plan whose root is a Filter or a Projection directly over a
+// reader: one AND-ed mask program for a Filter, one value program per
+// non-Column expr for a Projection (Column exprs yield no program). The same
+// compile entry points the operators use.
+bool debug_compile_programs(const uint8_t* data, size_t len,
+                            std::vector<ExprProgram>* progs,
+                            std::vector<int>* expr_index, std::string* err) {
+  auto td = decode_task_definition(data, len, err);
+  if (!td) return false;
+  const PlanNode* root = td->plan.get();
+  const PlanNode* in = nullptr;
+  if (root->kind == PlanNode::Filter) in = root->filter->input.get();
+  else if (root->kind == PlanNode::Projection)
+    in = root->projection->input.get();
+  else {
+    *err = "plan root must be a Filter or a Projection";
+    return false;
+  }
+  const Schema* sc = nullptr;
+  if (in && in->kind == PlanNode::FFIReader) sc = &in->ffi_reader->schema;
+  else if (in && in->kind == PlanNode::IpcReader) sc = &in->ipc_reader->schema;
+  if (!sc) {
+    *err = "the Filter / Projection input must be an FFIReader or IpcReader";
+    return false;
+  }
+  std::vector<DType> dts;
+  for (const Field& f : sc->fields) dts.push_back(f.dtype);
+  if (root->kind == PlanNode::Filter) {
+    ExprProgram p;
+    if (!compile_filter_program(root->filter->predicates, dts, &p, err))
+      return false;
+    progs->push_back(p);
+    expr_index->push_back(0);
+    return true;
+  }
+  const auto& exprs = root->projection->exprs;
+  for (size_t i = 0; i < exprs.size(); i++) {
+    if (exprs[i].kind == Expr::Column) continue;
+    ExprProgram p;
+    if (!compile_value_program(exprs[i], dts, &p, err)) {
+      *err = "expr " + std::to_string(i) + ": " + *err;
+      return false;
+    }
+    progs->push_back(p);
+    expr_index->push_back((int)i);
+  }
+  return true;
+}
+}  // namespace
+}  // namespace auron
+
+// test-only: compile the expressions of a Filter / Projection plan and render
+// the programs, one per line; "ERROR: <cause>" on a plan-build failure.
+// Host-only: needs no GPU.
+int32_t auron_debug_compile_expr(const uint8_t* data, size_t len, char* out,
+                                 size_t out_cap) {
+  std::vector<ExprProgram> progs;
+  std::vector<int> idx;
+  std::string err, s;
+  if (!debug_compile_programs(data, len, &progs, &idx, &err)) {
+    s = "ERROR: " + err;
+  } else {
+    for (size_t i = 0; i < progs.size(); i++)
+      s += "expr" + std::to_string(idx[i]) + " " +
+           expr_program_text(progs[i]) + "\n";
+  }
+  if (s.size() + 1 > out_cap) return -1;
+  memcpy(out, s.c_str(), s.size() + 1);
+  return (int32_t)s.size();
+}
+
+// test-only: run the compiled program of expression `expr_index` (0 for a
+// Filter) on host arrays through the interpreter that shares the kernel's
+// per-row evaluator. col_values[c] holds n values at column c's width,
+// col_valid[c] one byte per row or NULL. Writes n value bit patterns and n
+// states (0 valid, 1 null, 2 poison); returns the root type code (0 Int32,
+// 1 Int64, 2 Float64, 3 Bool) or -1 with the cause in err.
+int32_t auron_debug_eval_expr(const uint8_t* data, size_t len,
+                              int32_t expr_index, int32_t ncols,
+                              const void* const* col_values,
+                              const uint8_t* const* col_valid, int64_t n,
+                              uint64_t* out_bits, uint8_t* out_state,
+                              char* err_out, size_t err_cap) {
+  std::vector<ExprProgram> progs;
+  std::vector<int> idx;
+  std::string err;
+  const ExprProgram* prog = nullptr;
+  if (debug_compile_programs(data, len, &progs, &idx, &err)) {
+    for (size_t i = 0; i < progs.size(); i++)
+      if (idx[i] == expr_index) prog = &progs[i];
+    if (!prog) err = "no computed expression at index " +
+                     std::to_string(expr_index);
+  }
+  if (prog)
+    for (int s = 0; s < prog->nslots; s++)
+      if ((int64_t)prog->slot_col[s] >= ncols || !col_values[prog->slot_col[s]]) {
+        err = "input column " + std::to_string(prog->slot_col[s]) +
+              " not supplied";
+        prog = nullptr;
+        break;
+      }
+  if (!prog) {
+    snprintf(err_out, err_cap, "%s", err.c_str());
+    return -1;
+  }
+  std::vector<ExprHostCol> cols((size_t)ncols);
+  for (int32_t c = 0; c < ncols; c++)
+    cols[c] = ExprHostCol{col_values[c], col_valid ? col_valid[c] : nullptr};
+  expr_eval_host(*prog, cols, n, out_bits, out_state);
+  return (int32_t)prog->root_ty;
 }
 
 int64_t auron_get_metric(int64_t handle, const char* name) {

@@ -60,13 +60,25 @@ struct Expr {
     BinaryExpr, // PhysicalBinaryExprNode (auron.proto:172-176)
     IsNotNull,  // PhysicalIsNotNull (auron.proto:161-163)
     IsNull,     // PhysicalIsNull (auron.proto:155-157)
+    Not,        // PhysicalNot (auron.proto:163-165)
+    Negative,   // PhysicalNegativeNode (auron.proto:289-291)
+    Cast,       // PhysicalCastNode (auron.proto:284-287)
+    TryCast,    // PhysicalTryCastNode (auron.proto:279-282)
+    Case,       // PhysicalCaseNode (auron.proto:195-199)
+    SCAnd,      // PhysicalSCAndExprNode (auron.proto:300-303)
+    SCOr,       // PhysicalSCOrExprNode (auron.proto:305-308)
   } kind = Column;
   std::string col_name;
   uint32_t col_index = 0;
   // AggFunction enum: MIN=0 MAX=1 SUM=2 AVG=3 COUNT=4. Default 0 (MIN):
   // proto3 omits zero-valued enums on the wire, so an absent field IS MIN.
   int32_t agg_function = 0;
-  std::vector<Expr> children;  // agg args / binary l,r / null-check operand
+  // agg args / binary l,r / unary operand. Case: [base?] (when, then)*
+  // [else?], with case_has_base / case_has_else saying which ends exist.
+  std::vector<Expr> children;
+  bool case_has_base = false;
+  bool case_has_else = false;
+  DType cast_type = DType::Unsupported;  // Cast / TryCast arrow_type = 2
   DType return_type = DType::Unsupported;
   std::string op;              // binary op name (auron-serde/src/lib.rs:70-96)
   std::vector<uint8_t> literal_ipc;  // raw ScalarValue.ipc_bytes

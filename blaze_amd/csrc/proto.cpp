@@ -187,6 +187,82 @@ Expr decode_expr(Reader r, std::string* err) {
         }
         return e;
       }
+      case 8: case 12: {  // PhysicalNot / PhysicalNegativeNode {expr = 1}
+        Expr e;
+        e.kind = (n == 8) ? Expr::Not : Expr::Negative;
+        Reader s = r.sub();
+        while (true) {
+          auto [sf, sw] = s.tag();
+          if (sf == 0) break;
+          if (sf == 1) e.children.push_back(decode_expr(s.sub(), err));
+          else s.skip(sw);
+        }
+        return e;
+      }
+      case 9: {  // PhysicalCaseNode{expr=1, when_then_expr=2, else_expr=3}
+        Expr e;
+        e.kind = Expr::Case;
+        Reader s = r.sub();
+        std::vector<Expr> base, arms, els;
+        while (true) {
+          auto [sf, sw] = s.tag();
+          if (sf == 0) break;
+          if (sf == 1) {
+            base.push_back(decode_expr(s.sub(), err));
+          } else if (sf == 2) {  // PhysicalWhenThen{when_expr=1, then_expr=2}
+            Reader wt = s.sub();
+            Expr when, then;
+            bool hw = false, ht = false;
+            while (true) {
+              auto [wf, ww] = wt.tag();
+              if (wf == 0) break;
+              if (wf == 1) { when = decode_expr(wt.sub(), err); hw = true; }
+              else if (wf == 2) { then = decode_expr(wt.sub(), err); ht = true; }
+              else wt.skip(ww);
+            }
+            if ((!hw || !ht) && err->empty())
+              *err = "PhysicalWhenThen without when_expr/then_expr";
+            arms.push_back(std::move(when));
+            arms.push_back(std::move(then));
+          } else if (sf == 3) {
+            els.push_back(decode_expr(s.sub(), err));
+          } else {
+            s.skip(sw);
+          }
+        }
+        e.case_has_base = !base.empty();
+        e.case_has_else = !els.empty();
+        if (e.case_has_base) e.children.push_back(std::move(base[0]));
+        for (Expr& a : arms) e.children.push_back(std::move(a));
+        if (e.case_has_else) e.children.push_back(std::move(els[0]));
+        return e;
+      }
+      case 10: case 15: {  // PhysicalCastNode / PhysicalTryCastNode
+        Expr e;
+        e.kind = (n == 10) ? Expr::Cast : Expr::TryCast;
+        Reader s = r.sub();
+        while (true) {
+          auto [sf, sw] = s.tag();
+          if (sf == 0) break;
+          if (sf == 1) e.children.push_back(decode_expr(s.sub(), err));
+          else if (sf == 2) e.cast_type = decode_arrow_type(s.sub());
+          else s.skip(sw);
+        }
+        return e;
+      }
+      case 3000: case 3001: {  // PhysicalSCAnd/SCOrExprNode{left=1, right=2}
+        Expr e;
+        e.kind = (n == 3000) ? Expr::SCAnd : Expr::SCOr;
+        Reader s = r.sub();
+        while (true) {
+          auto [sf, sw] = s.tag();
+          if (sf == 0) break;
+          if (sf == 1 || sf == 2)
+            e.children.push_back(decode_expr(s.sub(), err));
+          else s.skip(sw);
+        }
+        return e;
+      }
       default:
         if (err->empty())
           *err = "unsupported PhysicalExprNode field " + std::to_string(n);

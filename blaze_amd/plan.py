@@ -319,7 +319,8 @@ def literal(value, dtype="int32"):
     import pyarrow as pa
 
     pa_type = {"int32": pa.int32(), "int64": pa.int64(),
-               "float64": pa.float64(), "utf8": pa.utf8()}[dtype]
+               "float64": pa.float64(), "utf8": pa.utf8(),
+               "bool": pa.bool_()}[dtype]
     # PhysicalExprNode{literal = 2} -> ScalarValue{ipc_bytes = 1}
     return _len_field(2, _len_field(1, literal_ipc(value, pa_type)))
 
@@ -332,6 +333,55 @@ def binary_expr(l, r, op):
 
 def is_not_null(child):
     return _len_field(7, _len_field(1, child))
+
+
+def is_null(child):
+    # PhysicalExprNode{is_null_expr = 6} -> PhysicalIsNull{expr = 1}
+    return _len_field(6, _len_field(1, child))
+
+
+def not_(child):
+    # PhysicalExprNode{not_expr = 8} -> PhysicalNot{expr = 1}
+    return _len_field(8, _len_field(1, child))
+
+
+def negative(child):
+    # PhysicalExprNode{negative = 12} -> PhysicalNegativeNode{expr = 1}
+    return _len_field(12, _len_field(1, child))
+
+
+def cast(child, dt_tag):
+    # PhysicalExprNode{cast = 10} -> PhysicalCastNode{expr=1, arrow_type=2}
+    return _len_field(10, _len_field(1, child) +
+                      _len_field(2, arrow_type(dt_tag)))
+
+
+def try_cast(child, dt_tag):
+    # PhysicalExprNode{try_cast = 15} -> PhysicalTryCastNode (same shape)
+    return _len_field(15, _len_field(1, child) +
+                      _len_field(2, arrow_type(dt_tag)))
+
+
+def case_when(whens, else_=None, base=None):
+    """PhysicalExprNode{case_ = 9} -> PhysicalCaseNode{expr=1,
+    when_then_expr=2{when_expr=1, then_expr=2}, else_expr=3}.
+    whens: list of (when_expr, then_expr)."""
+    node = _len_field(1, base) if base is not None else b""
+    for when, then in whens:
+        node += _len_field(2, _len_field(1, when) + _len_field(2, then))
+    if else_ is not None:
+        node += _len_field(3, else_)
+    return _len_field(9, node)
+
+
+def sc_and(l, r):
+    # PhysicalExprNode{sc_and_expr = 3000} -> PhysicalSCAndExprNode{l=1, r=2}
+    return _len_field(3000, _len_field(1, l) + _len_field(2, r))
+
+
+def sc_or(l, r):
+    # PhysicalExprNode{sc_or_expr = 3001} -> PhysicalSCOrExprNode{l=1, r=2}
+    return _len_field(3001, _len_field(1, l) + _len_field(2, r))
 
 
 def filter_node(input_plan, predicates):
