@@ -7,76 +7,32 @@
 //   AggExec         (agg_exec.rs:141-278, agg_table.rs, agg_ctx.rs) — GPU
 //   ShuffleWriterExec (shuffle_writer_exec.rs, sort_repartitioner.rs,
 //                      buffered_data.rs) — GPU partition + host file emit
+//   FilterExec / ProjectExec (filter_exec.rs, project_exec.rs) — GPU
+// This file holds the Arrow import/export, the operators and the Runtime that
+// drives the operator chain. The batch sources (ParquetScanExec,
+// IpcReaderExec) are in sources.cpp, the types and helpers they share with
+// this file in batch.h, the host-only auron_debug_* entry points in
+// debug_abi.cpp.
 // The GPU path is mandatory: any HIP failure aborts the task loudly; there is
 // no CPU fallback anywhere in this library.
 #include <chrono>
-#include <future>
-#include <thread>
 #include <tuple>
 #include <cstring>
-#include <atomic>
 #include <map>
 #include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
 
-#include "../../include/auron_hip.h"
-#include "dev.h"
+#include "batch.h"
 #include "expr.h"
 #include "kernels.h"
 #include "kernels_expr.h"
-#include "plan.h"
 #include "ipc_scalar.h"
-#include "parquet.h"
 #include "serde_host.h"
 
 namespace auron {
 namespace {
-
-struct EngineError : std::runtime_error {
-  using std::runtime_error::runtime_error;
-};
-
-// AURON_DEBUG=1 traces engine stages (with ms timestamps) to stderr
-static bool debug_on() {
-  static bool v = getenv("AURON_DEBUG") != nullptr;
-  return v;
-}
-static double dbg_ms() {
-  static auto t0 = std::chrono::steady_clock::now();
-  return std::chrono::duration<double, std::milli>(
-             std::chrono::steady_clock::now() - t0)
-      .count();
-}
-#define DBG(...)                                          \
-  do {                                                    \
-    if (debug_on()) {                                     \
-      fprintf(stderr, "[auron %9.2f] ", dbg_ms());        \
-      fprintf(stderr, __VA_ARGS__);                       \
-      fprintf(stderr, "\n");                              \
-      fflush(stderr);                                     \
-    }                                                     \
-  } while (0)
-
-#define FAIL(msg) throw EngineError(msg)
-
-// ---------------------------------------------------------------- columns --
-struct DevColumn {
-  DType dt = DType::Unsupported;
-  int64_t len = 0;
-  // non-owning views (point into own_* when owned)
-  const void* values = nullptr;       // prim: len*w; binary: data bytes
-  const uint8_t* validity = nullptr;  // LSB bitmap or null
-  const int32_t* offsets = nullptr;   // binary: len+1
-  int64_t data_len = 0;               // binary data bytes
-  DevBuf own_values, own_validity, own_offsets;
-};
-
-struct DevBatch {
-  int64_t num_rows = 0;
-  std::vector<DevColumn> cols;
-};
 
 const char* dtype_format(DType t) {
   switch (t) {
@@ -118,59 +74,36 @@ DType format_dtype(const char* f) {
 // ------------------------------------------------------------ arrow import --
 DevColumn import_child(const ArrowArray* a, DType dt, bool device,
                        hipStream_t stream) {
+  if (a->offset != 0) FAIL("ArrowArray with nonzero offset unsupported");
+  const bool binary = dt == DType::Binary || dt == DType::Utf8;
+  const size_t w = dtype_width(dt);
+  if (binary && a->n_buffers < 3) FAIL("binary array needs 3 buffers");
+  if (!binary && w == 0) FAIL("unsupported input dtype");
+  const uint8_t* validity_src = a->n_buffers > 0 && a->null_count != 0
+                                    ? (const uint8_t*)a->buffers[0]
+                                    : nullptr;
+  const int32_t* off_src = binary ? (const int32_t*)a->buffers[1] : nullptr;
+  const void* val_src = binary             ? a->buffers[2]
+                        : a->n_buffers > 1 ? a->buffers[1]
+                                           : nullptr;
+  if (!device)
+    return upload_column(dt, a->length, val_src,
+                         binary ? (size_t)off_src[a->length]
+                                : (size_t)a->length * w,
+                         off_src, validity_src, (a->length + 7) / 8, stream);
+  // device-resident input: borrow the caller's buffers
   DevColumn c;
   c.dt = dt;
   c.len = a->length;
-  if (a->offset != 0) FAIL("ArrowArray with nonzero offset unsupported");
-  size_t w = dtype_width(dt);
-  const void* validity_src = a->n_buffers > 0 ? a->buffers[0] : nullptr;
-  if (dt == DType::Binary || dt == DType::Utf8) {
-    if (a->n_buffers < 3) FAIL("binary array needs 3 buffers");
-    const int32_t* off_src = (const int32_t*)a->buffers[1];
-    const void* data_src = a->buffers[2];
-    if (device) {
-      c.offsets = off_src;
-      int32_t dl = 0;
-      AURON_HIP(hipMemcpyAsync(&dl, off_src + a->length, 4, hipMemcpyDeviceToHost,
-                               stream));
-      AURON_HIP(hipStreamSynchronize(stream));
-      c.data_len = dl;
-      c.values = data_src;
-    } else {
-      int32_t dl = off_src[a->length];
-      c.data_len = dl;
-      c.own_offsets.alloc((a->length + 1) * 4);
-      PinnedUploader::inst().copy(c.own_offsets.get(), off_src,
-                                  (a->length + 1) * 4, stream);
-      c.offsets = c.own_offsets.get<int32_t>();
-      if (dl > 0) {
-        c.own_values.alloc(dl);
-        PinnedUploader::inst().copy(c.own_values.get(), data_src, dl, stream);
-      }
-      c.values = c.own_values.get();
-    }
-  } else {
-    if (w == 0) FAIL("unsupported input dtype");
-    const void* val_src = a->n_buffers > 1 ? a->buffers[1] : nullptr;
-    if (device) {
-      c.values = val_src;
-    } else {
-      c.own_values.alloc(a->length * w);
-      PinnedUploader::inst().copy(c.own_values.get(), val_src,
-                                  (size_t)a->length * w, stream);
-      c.values = c.own_values.get();
-    }
-  }
-  if (validity_src && a->null_count != 0) {
-    size_t bl = (a->length + 7) / 8;
-    if (device) {
-      c.validity = (const uint8_t*)validity_src;
-    } else {
-      c.own_validity.alloc(bl);
-      AURON_HIP(hipMemcpyAsync(c.own_validity.get(), validity_src, bl,
-                               hipMemcpyHostToDevice, stream));
-      c.validity = c.own_validity.get<uint8_t>();
-    }
+  c.values = val_src;
+  c.validity = validity_src;
+  if (binary) {
+    c.offsets = off_src;
+    int32_t dl = 0;
+    AURON_HIP(hipMemcpyAsync(&dl, off_src + a->length, 4, hipMemcpyDeviceToHost,
+                             stream));
+    AURON_HIP(hipStreamSynchronize(stream));
+    c.data_len = dl;
   }
   return c;
 }
@@ -372,27 +305,6 @@ void export_batch(int64_t num_rows, std::vector<HostOutCol>&& cols,
   out->release = release_exported_array;
   out->private_data = priv;
 }
-
-// ------------------------------------------------------------------- conf --
-struct Conf {
-  AuronCallbacks* cb;
-  std::string get(const char* key, const std::string& dflt) const {
-    char buf[256];
-    buf[0] = '\0';
-    if (cb && cb->get_conf &&
-        cb->get_conf(cb->user, key, buf, sizeof(buf)) == 0 && buf[0] != '\0')
-      return std::string(buf);
-    return dflt;
-  }
-  int64_t get_i(const char* key, int64_t dflt) const {
-    std::string v = get(key, "");
-    return v.empty() ? dflt : (int64_t)strtoll(v.c_str(), nullptr, 10);
-  }
-  double get_d(const char* key, double dflt) const {
-    std::string v = get(key, "");
-    return v.empty() ? dflt : strtod(v.c_str(), nullptr);
-  }
-};
 
 // Variable-width output layout: device lens[n] (int32) -> host exclusive scan
 // -> the n+1 offsets, uploaded to d_offs and returned (the caller keeps the
@@ -2348,7 +2260,7 @@ class ShuffleOp {
     for (const DevBatch& b : staged_) n += b.num_rows;
     std::vector<int64_t> part_offsets(P_ + 1, 0);
     if (n == 0) {
-      write_files({}, part_offsets, 0);
+      write_files({}, part_offsets);
       return;
     }
     size_t ncols = staged_[0].cols.size();
@@ -2560,12 +2472,11 @@ class ShuffleOp {
       }
     }
     AURON_HIP(hipStreamSynchronize(stream_));
-    write_files(cols, part_offsets, n);
+    write_files(cols, part_offsets);
   }
 
   void write_files(const std::vector<HostCol>& cols,
-                   const std::vector<int64_t>& part_offsets, int64_t n) {
-    (void)n;
+                   const std::vector<int64_t>& part_offsets) {
     std::string err;
     if (!write_shuffle_files(cols, part_offsets, batch_size_,
                              node_.output_data_file, node_.output_index_file,
@@ -2668,12 +2579,8 @@ class FilterOp {
     }
     // stable compaction: positions = exclusive scan of mask
     DevBuf positions((n + 1) * 4);
-    size_t tb = 0;
-    scan_mask_u8(mask.get<uint8_t>(), positions.get<uint32_t>(), n, nullptr,
-                 &tb, stream_);
-    if (tb > scan_tmp_.size()) scan_tmp_.alloc(tb);
-    scan_mask_u8(mask.get<uint8_t>(), positions.get<uint32_t>(), n,
-                 scan_tmp_.get(), &tb, stream_);
+    scan_mask_positions(mask.get<uint8_t>(), n, positions.get<uint32_t>(),
+                        &scan_tmp_, stream_);
     if (!pinned_.get()) pinned_.alloc(8);
     uint32_t* h_cnt = pinned_.get<uint32_t>();
     AURON_HIP(hipMemcpyAsync(h_cnt, positions.get<uint32_t>() + n, 4,
@@ -3102,6 +3009,7 @@ struct Runtime {
 
     // pump input through the chain
     int64_t input_rows = 0;
+    const BatchSink sink = [&](DevBatch&& b) { feed(0, std::move(b)); };
     if (leaf->kind == PlanNode::FFIReader) {
       const FFIReaderNode& reader = *leaf->ffi_reader;
       while (true) {
@@ -3130,9 +3038,9 @@ struct Runtime {
         feed(0, std::move(b));
       }
     } else if (leaf->kind == PlanNode::IpcReader) {
-      input_rows = pump_ipc_reader(*leaf->ipc_reader);
+      input_rows = read_ipc(*leaf->ipc_reader, cb, ipc_codec_, stream, sink);
     } else {
-      input_rows = pump_parquet(*leaf->parquet);
+      input_rows = scan_parquet(*leaf->parquet, stream, sink);
     }
     // drain chain: pipeline breakers emit, transforms pass through
     AggOp* last_agg = nullptr;
@@ -3158,7 +3066,7 @@ struct Runtime {
             if (terminal) {
               outputs.push_back(std::move(ob));
             } else {
-              DevBatch b = host_out_to_dev(ob, st.agg->output_fields());
+              DevBatch b = host_out_to_dev(ob);
               feed(i + 1, std::move(b));
             }
           }
@@ -3187,581 +3095,6 @@ struct Runtime {
         std::chrono::duration_cast<std::chrono::nanoseconds>(
             std::chrono::steady_clock::now() - t0)
             .count();
-  }
-
-  // Evaluate a Column-vs-Literal pruning predicate against row-group stats:
-  // returns false only when the predicate PROVABLY excludes every row
-  // (parquet_exec.rs row-group stats pruning analog; conservative on any
-  // unsupported shape).
-  static bool rg_may_match(const Expr& e, const ParquetFile& pf, int rg) {
-    if (e.kind != Expr::BinaryExpr || e.children.size() != 2) return true;
-    if (e.op == "And")
-      return rg_may_match(e.children[0], pf, rg) &&
-             rg_may_match(e.children[1], pf, rg);
-    const Expr* col = nullptr;
-    const Expr* lit = nullptr;
-    bool flipped = false;
-    if (e.children[0].kind == Expr::Column &&
-        e.children[1].kind == Expr::Literal) {
-      col = &e.children[0];
-      lit = &e.children[1];
-    } else if (e.children[1].kind == Expr::Column &&
-               e.children[0].kind == Expr::Literal) {
-      col = &e.children[1];
-      lit = &e.children[0];
-      flipped = true;
-    } else {
-      return true;
-    }
-    if (col->col_index >= pf.columns().size()) return true;
-    PqColStats s = pf.column_stats(rg, (int)col->col_index);
-    if (!s.has_minmax) return true;
-    ScalarLit sl;
-    std::string err2;
-    if (!decode_ipc_scalar(lit->literal_ipc.data(), lit->literal_ipc.size(),
-                           &sl, &err2) ||
-        sl.is_null)
-      return true;
-    std::string op = e.op;
-    if (flipped) {
-      op = op == "Lt" ? "Gt" : op == "LtEq" ? "GtEq"
-           : op == "Gt" ? "Lt" : op == "GtEq" ? "LtEq" : op;
-    }
-    int pt = pf.columns()[col->col_index].physical_type;
-    if (pt == 1 || pt == 2) {
-      // compare in the int64 domain: a round-trip through double loses
-      // precision past 2^53 and could prune a row group that matches
-      int64_t lo = s.min_i, hi = s.max_i, v = sl.i64;
-      if (op == "Lt") return lo < v;
-      if (op == "LtEq") return lo <= v;
-      if (op == "Gt") return hi > v;
-      if (op == "GtEq") return hi >= v;
-      if (op == "Eq") return lo <= v && v <= hi;
-      return true;
-    }
-    if (pt != 4 && pt != 5) return true;
-    double lo = s.min_f, hi = s.max_f, v = sl.f64;
-    if (op == "Lt") return lo < v;
-    if (op == "LtEq") return lo <= v;
-    if (op == "Gt") return hi > v;
-    if (op == "GtEq") return hi >= v;
-    if (op == "Eq") return lo <= v && v <= hi;
-    return true;
-  }
-
-  // ParquetScanExec source (parquet_exec.rs:150-203; decode scope per
-  // parquet.h): footer/pages on host, validity/dictionary expansion on GPU.
-  int64_t pump_parquet(const ParquetScanNode& node) {
-    int64_t input_rows = 0;
-    DevBuf scan_tmp;
-    for (const std::string& path : node.files) {
-      ParquetFile pf(path);
-      const auto& fcols = pf.columns();
-      std::vector<uint32_t> proj = node.projection;
-      if (proj.empty())
-        for (uint32_t i = 0; i < fcols.size(); i++) proj.push_back(i);
-      for (uint32_t ci : proj)
-        if (ci >= fcols.size()) FAIL("parquet: projection out of range");
-      // host decode runs in ROW-GROUP WINDOWS overlapped with the device
-      // work: while window k's uploads/kernels/consume run on the stream,
-      // the host cores decode window k+1 (the host page-header walk +
-      // dict-prefix decode and the GPU page decompression are comparable
-      // in wall time — serializing them was ~40% of the config-3 step)
-      const int nrg = pf.num_row_groups();
-      const size_t width = proj.size();
-      std::vector<PqColumnChunkData> decoded((size_t)nrg * width);
-      std::string decode_err;
-      std::mutex err_mu;
-      const int RG_WIN = [&] {
-        const char* e = getenv("AURON_PARQUET_WIN");
-        if (e && e[0] == '0') return nrg > 0 ? nrg : 1;  // one window
-        if (e && atoi(e) > 0) return atoi(e);
-        // ~128M rows per window measured best at 1B rows (same-box A/B:
-        // 16-rg windows 1341 ms/step vs whole-file 1619, 8-rg 1679)
-        return std::max(1, (int)((512u << 20) /
-                                 std::max<int64_t>(
-                                     1, pf.row_group_rows(0) * 8)));
-      }();
-      auto decode_window = [&](int rg_lo, int rg_hi) {
-        size_t jlo = (size_t)rg_lo * width, jhi = (size_t)rg_hi * width;
-        unsigned nw = std::min<unsigned>(
-            std::min(48u, std::max(1u, std::thread::hardware_concurrency())),
-            (unsigned)(jhi - jlo));
-        std::atomic<size_t> next{jlo};
-        std::vector<std::thread> ws;
-        for (unsigned w = 0; w < nw; w++) {
-          ws.emplace_back([&]() {
-            for (;;) {
-              size_t i = next.fetch_add(1);
-              if (i >= jhi) break;
-              try {
-                decoded[i] =
-                    pf.read_chunk((int)(i / width), (int)proj[i % width]);
-              } catch (const std::exception& ex) {
-                std::lock_guard<std::mutex> lk(err_mu);
-                if (decode_err.empty()) decode_err = ex.what();
-              }
-            }
-          });
-        }
-        for (auto& w : ws) w.join();
-      };
-      std::future<void> pending = std::async(
-          std::launch::async, decode_window, 0, std::min(RG_WIN, nrg));
-      // ---- GPU page decompression batch (kernels_pq.hip) ----
-      // every gpu_comp chunk's PLAIN-suffix pages across ALL row groups go
-      // into ONE wave-per-page decompress+decode launch set (per-chunk
-      // launches would leave the chip nearly idle: ~30 pages per chunk).
-      // Results live in two blobs (validity bitmaps / dense values) that
-      // stay resident for the row-group assembly loop below.
-      struct GcResult {
-        uint64_t valid_base = 0, dense_base = 0;
-        int64_t total_nn = 0, null_total = 0;
-        bool ready = false;
-      };
-      std::vector<GcResult> gc_res((size_t)nrg * width);
-      for (int win_lo = 0; win_lo < nrg; win_lo += RG_WIN) {
-      const int win_hi = std::min(win_lo + RG_WIN, nrg);
-      pending.get();  // this window's host decode is complete
-      if (!decode_err.empty()) FAIL(decode_err);
-      if (win_hi < nrg)  // overlap: decode the NEXT window on host cores
-        pending = std::async(std::launch::async, decode_window, win_hi,
-                             std::min(win_hi + RG_WIN, nrg));
-      DevBuf d_gc_valid, d_gc_dense;
-      {
-        std::vector<PqGpuPage> pages;
-        std::vector<PqGpuChunk> chmeta;
-        std::vector<size_t> ch_di;
-        uint64_t comp_total = 0, scratch_total = 0, valid_total = 0,
-                 dense_total = 0;
-        auto al8 = [](uint64_t v) { return (v + 7) & ~7ull; };
-        for (size_t di = (size_t)win_lo * width;
-             di < (size_t)win_hi * width; di++) {
-          PqColumnChunkData& cd = decoded[di];
-          if (!cd.gpu_comp) continue;
-          const int vw = cd.value_width;
-          int64_t values = cd.prefix_values + cd.suffix_values;
-          PqGpuChunk ch;
-          ch.page0 = (uint32_t)pages.size();
-          ch.npages = (uint32_t)cd.comp_pages.size();
-          ch.valid_base = valid_total;
-          ch.dense_base = dense_total;
-          ch.prefix_nn = (uint32_t)(cd.plain.size() / (size_t)vw);
-          ch.vw = (uint32_t)vw;
-          uint32_t vbase = (uint32_t)cd.prefix_values;
-          for (const auto& pg : cd.comp_pages) {
-            PqGpuPage p;
-            p.comp_off = comp_total + (uint64_t)(pg.src - cd.comp_pages[0].src);
-            p.uncomp_off = scratch_total;
-            p.comp_len = pg.comp_len;
-            p.uncomp_len = pg.uncomp_len;
-            p.num_values = pg.num_values;
-            p.value_base = vbase;
-            p.has_def = cd.nullable ? 1u : 0u;
-            p.chunk_id = (uint32_t)chmeta.size();
-            pages.push_back(p);
-            vbase += pg.num_values;
-            scratch_total += al8(pg.uncomp_len);
-          }
-          const auto& lastp = cd.comp_pages.back();
-          comp_total += al8((uint64_t)(lastp.src - cd.comp_pages[0].src) +
-                            lastp.comp_len);
-          valid_total += al8(((uint64_t)values + 7) / 8);
-          dense_total += al8((uint64_t)values * vw);
-          chmeta.push_back(ch);
-          ch_di.push_back(di);
-        }
-        if (!pages.empty()) {
-          DevBuf d_comp(comp_total), d_scratch(scratch_total);
-          d_gc_valid.alloc(valid_total ? valid_total : 8);
-          d_gc_dense.alloc(dense_total);
-          DevBuf d_pages(pages.size() * sizeof(PqGpuPage));
-          DevBuf d_chunks(chmeta.size() * sizeof(PqGpuChunk));
-          DevBuf d_nn(pages.size() * 4), d_voff(pages.size() * 4);
-          DevBuf d_pdense(pages.size() * 4), d_chunknn(chmeta.size() * 4);
-          DevBuf d_gcerr(4);
-          AURON_HIP(hipMemsetAsync(d_gc_valid.get(), 0, valid_total, stream));
-          AURON_HIP(hipMemsetAsync(d_gcerr.get(), 0, 4, stream));
-          PinnedUploader::inst().copy(d_pages.get(), pages.data(),
-                                      pages.size() * sizeof(PqGpuPage),
-                                      stream);
-          PinnedUploader::inst().copy(d_chunks.get(), chmeta.data(),
-                                      chmeta.size() * sizeof(PqGpuChunk),
-                                      stream);
-          std::vector<std::vector<uint8_t>> pvbits(chmeta.size());
-          for (size_t c = 0; c < chmeta.size(); c++) {
-            PqColumnChunkData& cd = decoded[ch_di[c]];
-            // compressed span (pages of a chunk are contiguous in the file)
-            const auto& p0 = cd.comp_pages[0];
-            const auto& pl = cd.comp_pages.back();
-            size_t span = (size_t)(pl.src - p0.src) + pl.comp_len;
-            PinnedUploader::inst().copy(
-                d_comp.get<uint8_t>() + pages[chmeta[c].page0].comp_off -
-                    (uint64_t)(p0.src - cd.comp_pages[0].src),
-                p0.src, span, stream);
-            // host-decoded prefix: dense values + validity bits
-            if (!cd.plain.empty())
-              PinnedUploader::inst().copy(
-                  d_gc_dense.get<uint8_t>() + chmeta[c].dense_base,
-                  cd.plain.data(), cd.plain.size(), stream);
-            if (cd.nullable && cd.prefix_values > 0) {
-              size_t pb = ((size_t)cd.prefix_values + 7) / 8;
-              auto& vb = pvbits[c];
-              if (!cd.validity.empty()) {
-                vb.assign(cd.validity.begin(), cd.validity.begin() + pb);
-              } else {
-                vb.assign(pb, 0xFF);
-              }
-              if (cd.prefix_values & 7)  // clear bits beyond the prefix:
-                vb[pb - 1] &= (uint8_t)((1u << (cd.prefix_values & 7)) - 1);
-              PinnedUploader::inst().copy(
-                  d_gc_valid.get<uint8_t>() + chmeta[c].valid_base, vb.data(),
-                  pb, stream);
-            }
-          }
-          launch_pq_pages_decode(d_comp.get<uint8_t>(),
-                                 d_pages.get<PqGpuPage>(), (int)pages.size(),
-                                 d_scratch.get<uint8_t>(),
-                                 d_gc_valid.get<uint8_t>(),
-                                 d_chunks.get<PqGpuChunk>(),
-                                 d_nn.get<uint32_t>(), d_voff.get<uint32_t>(),
-                                 d_gcerr.get<uint32_t>(), stream);
-          launch_pq_page_offsets(d_chunks.get<PqGpuChunk>(),
-                                 (int)chmeta.size(), d_nn.get<uint32_t>(),
-                                 d_pdense.get<uint32_t>(),
-                                 d_chunknn.get<uint32_t>(), stream);
-          launch_pq_pages_compact(d_pages.get<PqGpuPage>(),
-                                  (int)pages.size(),
-                                  d_scratch.get<uint8_t>(),
-                                  d_chunks.get<PqGpuChunk>(),
-                                  d_nn.get<uint32_t>(),
-                                  d_voff.get<uint32_t>(),
-                                  d_pdense.get<uint32_t>(),
-                                  d_gc_dense.get<uint8_t>(), stream);
-          std::vector<uint32_t> h_chunknn(chmeta.size());
-          uint32_t h_err = 0;
-          AURON_HIP(hipMemcpyAsync(h_chunknn.data(), d_chunknn.get(),
-                                   chmeta.size() * 4, hipMemcpyDeviceToHost,
-                                   stream));
-          AURON_HIP(hipMemcpyAsync(&h_err, d_gcerr.get(), 4,
-                                   hipMemcpyDeviceToHost, stream));
-          AURON_HIP(hipStreamSynchronize(stream));
-          if (h_err) FAIL("parquet: GPU page decode failed (flags " +
-                          std::to_string(h_err) + ")");
-          for (size_t c = 0; c < chmeta.size(); c++) {
-            PqColumnChunkData& cd = decoded[ch_di[c]];
-            GcResult& r = gc_res[ch_di[c]];
-            r.valid_base = chmeta[c].valid_base;
-            r.dense_base = chmeta[c].dense_base;
-            r.total_nn = (int64_t)chmeta[c].prefix_nn + h_chunknn[c];
-            r.null_total =
-                cd.prefix_values + cd.suffix_values - r.total_nn;
-            r.ready = true;
-          }
-        }
-      }
-      for (int rg = win_lo; rg < win_hi; rg++) {
-        bool keep = true;
-        for (const Expr& pr : node.pruning)
-          keep = keep && rg_may_match(pr, pf, rg);
-        if (!keep) {
-          DBG("parquet: pruned row group %d", rg);
-          continue;
-        }
-        int64_t rows = pf.row_group_rows(rg);
-        DevBatch b;
-        b.num_rows = rows;
-        for (size_t pi = 0; pi < width; pi++) {
-          uint32_t ci = proj[pi];
-          PqColumnChunkData cd = std::move(decoded[(size_t)rg * width + pi]);
-          DevColumn c;
-          c.dt = fcols[ci].dtype();
-          c.len = rows;
-          bool has_nulls = cd.null_count > 0;
-          if (cd.gpu_comp) {
-            // device-decompressed chunk: validity bitmap + dense values are
-            // already resident in the batch blobs (pre-pass above)
-            const GcResult& r = gc_res[(size_t)rg * width + pi];
-            if (!r.ready) FAIL("parquet: gpu page results missing");
-            if (cd.prefix_values + cd.suffix_values != rows)
-              FAIL("parquet: gpu chunk row count mismatch");
-            const int w2 = (int)dtype_width(fcols[ci].dtype());
-            c.own_values.alloc((size_t)rows * w2);
-            const uint8_t* dense = d_gc_dense.get<uint8_t>() + r.dense_base;
-            if (r.null_total == 0) {
-              AURON_HIP(hipMemcpyAsync(c.own_values.get(), dense,
-                                       (size_t)rows * w2,
-                                       hipMemcpyDeviceToDevice, stream));
-            } else {
-              c.own_validity.alloc((rows + 7) / 8);
-              AURON_HIP(hipMemcpyAsync(c.own_validity.get(),
-                                       d_gc_valid.get<uint8_t>() +
-                                           r.valid_base,
-                                       (size_t)(rows + 7) / 8,
-                                       hipMemcpyDeviceToDevice, stream));
-              c.validity = c.own_validity.get<uint8_t>();
-              DevBuf d_mask2(rows), d_pos2((rows + 1) * 4);
-              launch_bits_to_mask(c.validity, rows, d_mask2.get<uint8_t>(),
-                                  stream);
-              size_t tb = 0;
-              scan_mask_u8(d_mask2.get<uint8_t>(), d_pos2.get<uint32_t>(),
-                           rows, nullptr, &tb, stream);
-              if (tb > scan_tmp.size()) scan_tmp.alloc(tb);
-              scan_mask_u8(d_mask2.get<uint8_t>(), d_pos2.get<uint32_t>(),
-                           rows, scan_tmp.get(), &tb, stream);
-              launch_scatter_packed(w2, dense, d_pos2.get<uint32_t>(),
-                                    d_mask2.get<uint8_t>(), rows,
-                                    c.own_values.get<uint8_t>(), stream);
-              AURON_HIP(hipStreamSynchronize(stream));  // temps die here
-            }
-            c.values = c.own_values.get();
-            b.cols.push_back(std::move(c));
-            continue;
-          }
-          if (c.dt == DType::Utf8 || c.dt == DType::Binary) {
-            // row-aligned offsets/data assembled on host (parquet.cpp)
-            c.own_offsets.alloc((rows + 1) * 4);
-            AURON_HIP(hipMemcpyAsync(c.own_offsets.get(),
-                                     cd.bin_offsets.data(), (rows + 1) * 4,
-                                     hipMemcpyHostToDevice, stream));
-            c.offsets = c.own_offsets.get<int32_t>();
-            c.data_len = (int64_t)cd.bin_data.size();
-            c.own_values.alloc(cd.bin_data.empty() ? 1 : cd.bin_data.size());
-            if (!cd.bin_data.empty())
-              PinnedUploader::inst().copy(c.own_values.get(),
-                                          cd.bin_data.data(),
-                                          cd.bin_data.size(), stream);
-            c.values = c.own_values.get();
-            if (has_nulls) {
-              c.own_validity.alloc(cd.validity.size());
-              AURON_HIP(hipMemcpyAsync(c.own_validity.get(),
-                                       cd.validity.data(), cd.validity.size(),
-                                       hipMemcpyHostToDevice, stream));
-              c.validity = c.own_validity.get<uint8_t>();
-            }
-            AURON_HIP(hipStreamSynchronize(stream));
-            b.cols.push_back(std::move(c));
-            continue;
-          }
-          const int w = (int)dtype_width(fcols[ci].dtype());
-          c.own_values.alloc((size_t)rows * w);
-          DevBuf d_valid, d_mask, d_positions, d_packed, d_indices;
-          DevBuf d_runs, d_runbytes;
-          if (cd.gpu_def) {
-            // def levels expand to the validity bitmap ON DEVICE (the host
-            // only walked the run headers — parquet.cpp rle_bp_runs)
-            d_runs.alloc(cd.def_runs.size() * sizeof(PqRun));
-            PinnedUploader::inst().copy(d_runs.get(), cd.def_runs.data(),
-                                        cd.def_runs.size() * sizeof(PqRun),
-                                        stream);
-            d_runbytes.alloc(cd.def_bytes.empty() ? 8 : cd.def_bytes.size());
-            if (!cd.def_bytes.empty())
-              PinnedUploader::inst().copy(d_runbytes.get(),
-                                          cd.def_bytes.data(),
-                                          cd.def_bytes.size(), stream);
-            c.own_validity.alloc((rows + 7) / 8);
-            launch_def_expand_validity(d_runs.get(), (int)cd.def_runs.size(),
-                                       d_runbytes.get<uint8_t>(), rows,
-                                       c.own_validity.get<uint8_t>(), stream);
-            c.validity = c.own_validity.get<uint8_t>();
-            d_mask.alloc(rows);
-            launch_bits_to_mask(c.validity, rows, d_mask.get<uint8_t>(),
-                                stream);
-            d_positions.alloc((rows + 1) * 4);
-            size_t tb = 0;
-            scan_mask_u8(d_mask.get<uint8_t>(), d_positions.get<uint32_t>(),
-                         rows, nullptr, &tb, stream);
-            if (tb > scan_tmp.size()) scan_tmp.alloc(tb);
-            scan_mask_u8(d_mask.get<uint8_t>(), d_positions.get<uint32_t>(),
-                         rows, scan_tmp.get(), &tb, stream);
-          } else if (has_nulls) {
-            c.own_validity.alloc(cd.validity.size());
-            AURON_HIP(hipMemcpyAsync(c.own_validity.get(), cd.validity.data(),
-                                     cd.validity.size(), hipMemcpyHostToDevice,
-                                     stream));
-            c.validity = c.own_validity.get<uint8_t>();
-            d_mask.alloc(rows);
-            launch_bits_to_mask(c.validity, rows, d_mask.get<uint8_t>(),
-                                stream);
-            d_positions.alloc((rows + 1) * 4);
-            size_t tb = 0;
-            scan_mask_u8(d_mask.get<uint8_t>(), d_positions.get<uint32_t>(),
-                         rows, nullptr, &tb, stream);
-            if (tb > scan_tmp.size()) scan_tmp.alloc(tb);
-            scan_mask_u8(d_mask.get<uint8_t>(), d_positions.get<uint32_t>(),
-                         rows, scan_tmp.get(), &tb, stream);
-          }
-          if (cd.gpu_dict) {
-            // dictionary indices: host walked run headers only; expand the
-            // dense non-null index array on device, then scatter/gather as
-            // in the host-materialized path
-            DevBuf d_iruns(cd.idx_runs.size() * sizeof(PqRun));
-            PinnedUploader::inst().copy(d_iruns.get(), cd.idx_runs.data(),
-                                        cd.idx_runs.size() * sizeof(PqRun),
-                                        stream);
-            DevBuf d_ibytes(cd.idx_bytes.empty() ? 8 : cd.idx_bytes.size());
-            if (!cd.idx_bytes.empty())
-              PinnedUploader::inst().copy(d_ibytes.get(), cd.idx_bytes.data(),
-                                          cd.idx_bytes.size(), stream);
-            DevBuf d_idx_packed((cd.nn_count ? cd.nn_count : 1) * 4);
-            launch_runs_expand_u32(d_iruns.get(), (int)cd.idx_runs.size(),
-                                   d_ibytes.get<uint8_t>(), cd.nn_count,
-                                   d_idx_packed.get<uint32_t>(), stream);
-            d_indices.alloc((size_t)rows * 4);
-            if (has_nulls) {
-              launch_scatter_packed(4, d_idx_packed.get<uint8_t>(),
-                                    d_positions.get<uint32_t>(),
-                                    d_mask.get<uint8_t>(), rows,
-                                    d_indices.get<uint8_t>(), stream);
-            } else {
-              AURON_HIP(hipMemcpyAsync(d_indices.get(), d_idx_packed.get(),
-                                       (size_t)rows * 4,
-                                       hipMemcpyDeviceToDevice, stream));
-            }
-            DevBuf d_dict(cd.dict_values.empty() ? 1 : cd.dict_values.size());
-            if (!cd.dict_values.empty())
-              AURON_HIP(hipMemcpyAsync(d_dict.get(), cd.dict_values.data(),
-                                       cd.dict_values.size(),
-                                       hipMemcpyHostToDevice, stream));
-            if (w == 8)
-              launch_gather_8(d_dict.get<uint8_t>(),
-                              d_indices.get<uint32_t>(), rows,
-                              c.own_values.get<uint8_t>(), stream);
-            else
-              launch_gather_4(d_dict.get<uint8_t>(),
-                              d_indices.get<uint32_t>(), rows,
-                              c.own_values.get<uint8_t>(), stream);
-            AURON_HIP(hipStreamSynchronize(stream));  // temps die below
-          } else if (!cd.uses_dict) {
-            // PLAIN: non-null values packed densely
-            if (!has_nulls) {
-              PinnedUploader::inst().copy(c.own_values.get(), cd.plain.data(),
-                                          cd.plain.size(), stream);
-            } else {
-              d_packed.alloc(cd.plain.empty() ? 1 : cd.plain.size());
-              if (!cd.plain.empty())
-                PinnedUploader::inst().copy(d_packed.get(), cd.plain.data(),
-                                            cd.plain.size(), stream);
-              launch_scatter_packed(w, d_packed.get<uint8_t>(),
-                                    d_positions.get<uint32_t>(),
-                                    d_mask.get<uint8_t>(), rows,
-                                    c.own_values.get<uint8_t>(), stream);
-            }
-          } else {
-            // dictionary: expand packed indices to rows, gather dict values
-            d_indices.alloc((size_t)rows * 4);
-            DevBuf d_idx_packed(cd.dict_indices.empty()
-                                    ? 4
-                                    : cd.dict_indices.size() * 4);
-            if (!cd.dict_indices.empty())
-              PinnedUploader::inst().copy(d_idx_packed.get(),
-                                          cd.dict_indices.data(),
-                                          cd.dict_indices.size() * 4, stream);
-            if (has_nulls) {
-              launch_scatter_packed(4, d_idx_packed.get<uint8_t>(),
-                                    d_positions.get<uint32_t>(),
-                                    d_mask.get<uint8_t>(), rows,
-                                    d_indices.get<uint8_t>(), stream);
-            } else {
-              AURON_HIP(hipMemcpyAsync(d_indices.get(), d_idx_packed.get(),
-                                       (size_t)rows * 4,
-                                       hipMemcpyDeviceToDevice, stream));
-            }
-            DevBuf d_dict(cd.dict_values.empty() ? 1 : cd.dict_values.size());
-            if (!cd.dict_values.empty())
-              AURON_HIP(hipMemcpyAsync(d_dict.get(), cd.dict_values.data(),
-                                       cd.dict_values.size(),
-                                       hipMemcpyHostToDevice, stream));
-            if (w == 8)
-              launch_gather_8(d_dict.get<uint8_t>(),
-                              d_indices.get<uint32_t>(), rows,
-                              c.own_values.get<uint8_t>(), stream);
-            else
-              launch_gather_4(d_dict.get<uint8_t>(),
-                              d_indices.get<uint32_t>(), rows,
-                              c.own_values.get<uint8_t>(), stream);
-          }
-          AURON_HIP(hipStreamSynchronize(stream));  // host cd dies here
-          c.values = c.own_values.get();
-          b.cols.push_back(std::move(c));
-        }
-        input_rows += rows;
-        feed(0, std::move(b));
-      }
-      }  // row-group window
-    }
-    return input_rows;
-  }
-
-  // IpcReaderExec source (ipc_reader_exec.rs:62-120): raw shuffle block
-  // streams in, decoded+deserialized on host, batches up to the device.
-  int64_t pump_ipc_reader(const IpcReaderNode& reader) {
-    if (!cb.next_ipc_bytes)
-      FAIL("plan holds IpcReaderExec but no next_ipc_bytes callback was given");
-    std::vector<int> widths;
-    for (const Field& f : reader.schema.fields) {
-      if (f.dtype == DType::Binary || f.dtype == DType::Utf8)
-        widths.push_back(0);
-      else if (dtype_width(f.dtype) > 0)
-        widths.push_back((int)dtype_width(f.dtype));
-      else
-        FAIL("IpcReader: unsupported column dtype");
-    }
-    int64_t input_rows = 0;
-    while (true) {
-      const uint8_t* data = nullptr;
-      size_t len = 0;
-      int rc = cb.next_ipc_bytes(cb.user, reader.resource_id.c_str(), &data,
-                                 &len);
-      DBG("ipc reader rc=%d len=%zu", rc, len);
-      if (rc == 0) break;
-      std::vector<uint8_t> payload;
-      std::string err;
-      if (!ipc_decode_blocks(data, len, &payload, &err, ipc_codec_))
-        FAIL(err);
-      size_t used = 0;
-      while (used < payload.size()) {
-        int64_t rows = 0;
-        std::vector<OwnedCol> cols;
-        if (!serde_read_batch(payload.data(), payload.size(), &used, widths,
-                              &rows, &cols, &err))
-          FAIL(err);
-        DevBatch b;
-        b.num_rows = rows;
-        for (size_t ci = 0; ci < cols.size(); ci++) {
-          OwnedCol& oc = cols[ci];
-          DevColumn c;
-          c.dt = reader.schema.fields[ci].dtype;
-          c.len = rows;
-          if (oc.byte_width == 0) {
-            c.own_offsets.alloc((rows + 1) * 4);
-            AURON_HIP(hipMemcpyAsync(c.own_offsets.get(), oc.offsets.data(),
-                                     (rows + 1) * 4, hipMemcpyHostToDevice,
-                                     stream));
-            c.offsets = c.own_offsets.get<int32_t>();
-            c.data_len = (int64_t)oc.values.size();
-          }
-          c.own_values.alloc(oc.values.empty() ? 1 : oc.values.size());
-          if (!oc.values.empty())
-            AURON_HIP(hipMemcpyAsync(c.own_values.get(), oc.values.data(),
-                                     oc.values.size(), hipMemcpyHostToDevice,
-                                     stream));
-          c.values = c.own_values.get();
-          if (!oc.validity.empty()) {
-            c.own_validity.alloc(oc.validity.size());
-            AURON_HIP(hipMemcpyAsync(c.own_validity.get(), oc.validity.data(),
-                                     oc.validity.size(), hipMemcpyHostToDevice,
-                                     stream));
-            c.validity = c.own_validity.get<uint8_t>();
-          }
-          AURON_HIP(hipStreamSynchronize(stream));  // host vectors die below
-          b.cols.push_back(std::move(c));
-        }
-        input_rows += rows;
-        feed(0, std::move(b));
-      }
-    }
-    return input_rows;
   }
 
   void feed(size_t idx, DevBatch&& b) {
@@ -3880,43 +3213,17 @@ struct Runtime {
     outputs.emplace_back(n, std::move(cols));
   }
 
-  DevBatch host_out_to_dev(const std::pair<int64_t, std::vector<HostOutCol>>& ob,
-                           const std::vector<OutField>& fields) {
+  // a non-terminal Agg's staged host output, back up for the next stage
+  DevBatch host_out_to_dev(
+      const std::pair<int64_t, std::vector<HostOutCol>>& ob) {
     DevBatch b;
     b.num_rows = ob.first;
-    for (size_t i = 0; i < ob.second.size(); i++) {
-      const HostOutCol& h = ob.second[i];
-      DevColumn c;
-      c.dt = h.dt;
-      c.len = ob.first;
-      if (h.dt == DType::Binary || h.dt == DType::Utf8) {
-        c.own_offsets.alloc(h.offsets.size() * 4);
-        AURON_HIP(hipMemcpyAsync(c.own_offsets.get(), h.offsets.data(),
-                                 h.offsets.size() * 4, hipMemcpyHostToDevice,
-                                 stream));
-        c.offsets = c.own_offsets.get<int32_t>();
-        c.data_len = (int64_t)h.values.size();
-        c.own_values.alloc(h.values.empty() ? 1 : h.values.size());
-        if (!h.values.empty())
-          AURON_HIP(hipMemcpyAsync(c.own_values.get(), h.values.data(),
-                                   h.values.size(), hipMemcpyHostToDevice,
-                                   stream));
-        c.values = c.own_values.get();
-      } else {
-        c.own_values.alloc(h.values.size());
-        PinnedUploader::inst().copy(c.own_values.get(), h.values.data(),
-                                    h.values.size(), stream);
-        c.values = c.own_values.get();
-      }
-      if (!h.validity.empty()) {
-        c.own_validity.alloc(h.validity.size());
-        AURON_HIP(hipMemcpyAsync(c.own_validity.get(), h.validity.data(),
-                                 h.validity.size(), hipMemcpyHostToDevice,
-                                 stream));
-        c.validity = c.own_validity.get<uint8_t>();
-      }
-      (void)fields;
-      b.cols.push_back(std::move(c));
+    for (const HostOutCol& h : ob.second) {
+      const bool binary = h.dt == DType::Binary || h.dt == DType::Utf8;
+      b.cols.push_back(upload_column(
+          h.dt, ob.first, h.values.data(), h.values.size(),
+          binary ? h.offsets.data() : nullptr, h.validity.data(),
+          h.validity.size(), stream));
     }
     return b;
   }
@@ -4044,183 +3351,6 @@ void auron_on_exit(void) {
 }
 
 const char* auron_version(void) { return "auron-hip 0.1 gfx950"; }
-
-// test-only: host-side batch_serde + IPC block codec roundtrip over a
-// 3-column batch (i64 key, f64 val, binary) — CPU-checkable byte parity
-// against the oracle writer plus write->read self-consistency, covering the
-// engine's IpcReader decode path without a GPU. Returns the block-stream
-// length (copied into out up to cap), or -1 with the error text in out.
-int64_t auron_debug_serde_roundtrip(const int64_t* k, const uint8_t* kvalid,
-                                    const double* v, const uint8_t* vvalid,
-                                    const int32_t* boffs, const uint8_t* bdata,
-                                    int64_t n, int64_t batch_size, uint8_t* out,
-                                    size_t cap) {
-  auto fail = [&](const std::string& m) -> int64_t {
-    snprintf((char*)out, cap, "%s", m.c_str());
-    return -1;
-  };
-  std::string err;
-  std::vector<HostCol> cols(3);
-  cols[0] = {8, (const uint8_t*)k, kvalid, nullptr};
-  cols[1] = {8, (const uint8_t*)v, vvalid, nullptr};
-  cols[2] = {0, bdata, nullptr, boffs};
-  IpcBlockWriter w;
-  for (int64_t beg = 0; beg < n; beg += batch_size) {
-    int64_t end = std::min(n, beg + batch_size);
-    std::vector<uint8_t> payload;
-    serde_write_batch(cols, beg, end, &payload);
-    if (!w.write_payload(payload.data(), payload.size(), &err))
-      return fail(err);
-  }
-  if (!w.finish_block(&err)) return fail(err);
-  std::vector<uint8_t> stream = w.take();
-
-  // decode side: blocks -> payload -> batches; verify every row round-trips
-  std::vector<uint8_t> payload;
-  if (!ipc_decode_blocks(stream.data(), stream.size(), &payload, &err))
-    return fail(err);
-  size_t pos = 0;
-  int64_t row = 0;
-  while (pos < payload.size()) {
-    size_t used = 0;
-    int64_t rows = 0;
-    std::vector<OwnedCol> rc;
-    if (!serde_read_batch(payload.data() + pos, payload.size() - pos, &used,
-                          {8, 8, 0}, &rows, &rc, &err))
-      return fail(err);
-    pos += used;
-    for (int64_t i = 0; i < rows; i++, row++) {
-      bool kv2 = rc[0].validity.empty() ||
-                 ((rc[0].validity[i >> 3] >> (i & 7)) & 1);
-      bool kv1 = !kvalid || ((kvalid[row >> 3] >> (row & 7)) & 1);
-      if (kv1 != kv2) return fail("key validity mismatch");
-      if (kv1 && memcmp(rc[0].values.data() + i * 8, (const uint8_t*)&k[row],
-                        8) != 0)
-        return fail("key value mismatch");
-      bool vv2 = rc[1].validity.empty() ||
-                 ((rc[1].validity[i >> 3] >> (i & 7)) & 1);
-      bool vv1 = !vvalid || ((vvalid[row >> 3] >> (row & 7)) & 1);
-      if (vv1 != vv2) return fail("val validity mismatch");
-      if (vv1 && memcmp(rc[1].values.data() + i * 8, (const uint8_t*)&v[row],
-                        8) != 0)
-        return fail("val value mismatch");
-      int32_t l1 = boffs[row + 1] - boffs[row];
-      int32_t l2 = rc[2].offsets[i + 1] - rc[2].offsets[i];
-      if (l1 != l2) return fail("binary length mismatch");
-      if (l1 && memcmp(rc[2].values.data() + rc[2].offsets[i],
-                       bdata + boffs[row], l1) != 0)
-        return fail("binary bytes mismatch");
-    }
-  }
-  if (row != n) return fail("row count mismatch");
-  if (stream.size() <= cap) memcpy(out, stream.data(), stream.size());
-  return (int64_t)stream.size();
-}
-
-// test-only: parse a parquet file on the host and summarize chunk decode
-// results (CPU-checkable against pyarrow metadata — no GPU needed)
-int32_t auron_debug_parquet_summary(const char* path, char* out, size_t cap) {
-  std::string r;
-  try {
-    ParquetFile pf(path);
-    r = "cols=";
-    for (const auto& c : pf.columns())
-      r += c.name + ":" + std::to_string(c.physical_type) +
-           (c.nullable ? "?" : "") + ",";
-    r += " rgs=" + std::to_string(pf.num_row_groups());
-    for (int rg = 0; rg < pf.num_row_groups(); rg++) {
-      r += " [rg" + std::to_string(rg) + " rows=" +
-           std::to_string(pf.row_group_rows(rg));
-      for (size_t c = 0; c < pf.columns().size(); c++) {
-        PqColumnChunkData cd = pf.read_chunk(rg, (int)c);
-        pq_materialize_gpu_staging(&cd);  // host-expand staged GPU runs
-        // value checksum: wrapping i64 sum of the raw fixed-width values
-        // (sign-extended for narrow ints) over the dense non-null stream —
-        // lets CPU tests verify DECODED VALUES against numpy ground truth,
-        // not just counts
-        int64_t csum = 0;
-        const size_t w = dtype_width(pf.columns()[c].dtype());
-        auto add_vals = [&](const uint8_t* v, size_t cnt) {
-          for (size_t i = 0; i < cnt; i++) {
-            int64_t x = 0;
-            if (w == 8) {
-              memcpy(&x, v + i * 8, 8);
-            } else if (w == 4) {
-              int32_t x32;
-              memcpy(&x32, v + i * 4, 4);
-              x = x32;
-            }
-            csum = (int64_t)((uint64_t)csum + (uint64_t)x);
-          }
-        };
-        if (w > 0) {
-          if (cd.uses_dict) {
-            for (uint32_t ix : cd.dict_indices)
-              add_vals(cd.dict_values.data() + (size_t)ix * w, 1);
-          } else {
-            add_vals(cd.plain.data(), cd.plain.size() / w);
-          }
-        } else if (!cd.bin_offsets.empty()) {
-          // byte-array columns: position-weighted rolling checksum over the
-          // row-aligned lengths and data bytes
-          for (size_t i = 0; i + 1 < cd.bin_offsets.size(); i++) {
-            int64_t l = cd.bin_offsets[i + 1] - cd.bin_offsets[i];
-            csum = (int64_t)((uint64_t)csum + (uint64_t)(l * (int64_t)(i + 1)));
-          }
-          for (size_t j = 0; j < cd.bin_data.size(); j++)
-            csum = (int64_t)((uint64_t)csum +
-                             (uint64_t)((int64_t)cd.bin_data[j] *
-                                        (int64_t)(j + 1)));
-        }
-        r += " c" + std::to_string(c) + "{n=" + std::to_string(cd.num_values) +
-             ",nulls=" + std::to_string(cd.null_count) +
-             ",dict=" + std::to_string(cd.uses_dict ? cd.dict_count : 0) +
-             ",csum=" + std::to_string(csum) + "}";
-      }
-      r += "]";
-    }
-  } catch (const std::exception& ex) {
-    r = std::string("ERROR: ") + ex.what();
-  }
-  if (r.size() + 1 > cap) return -1;
-  memcpy(out, r.c_str(), r.size() + 1);
-  return (int32_t)r.size();
-}
-
-// test-only: decode a ScalarValue ipc_bytes literal and render it
-int32_t auron_debug_decode_scalar(const uint8_t* data, size_t len, char* out,
-                                  size_t cap) {
-  ScalarLit s;
-  std::string err;
-  std::string r;
-  if (!decode_ipc_scalar(data, len, &s, &err)) {
-    r = "ERROR: " + err;
-  } else if (s.is_null) {
-    r = "null dtype=" + std::to_string((int)s.dtype);
-  } else if (s.dtype == DType::Utf8 || s.dtype == DType::Binary) {
-    r = "str:" + s.utf8;
-  } else if (s.dtype == DType::Float64 || s.dtype == DType::Float32) {
-    char buf[64];
-    snprintf(buf, sizeof(buf), "f:%.17g", s.f64);
-    r = buf;
-  } else {
-    r = "i:" + std::to_string(s.i64) + " dtype=" + std::to_string((int)s.dtype);
-  }
-  if (r.size() + 1 > cap) return -1;
-  memcpy(out, r.c_str(), r.size() + 1);
-  return (int32_t)r.size();
-}
-
-// test-only: exercise the get_conf callback plumbing from the C side (the
-// ctypes out-param contract is easy to get wrong — see GET_CONF note)
-int32_t auron_debug_conf_roundtrip(AuronCallbacks* cb, const char* key,
-                                   char* out, size_t cap) {
-  Conf conf{cb};
-  std::string v = conf.get(key, "<default>");
-  if (v.size() + 1 > cap) return -1;
-  memcpy(out, v.c_str(), v.size() + 1);
-  return (int32_t)v.size();
-}
 
 // Compute murmur3(seed 42) + pmod partition ids for host-resident i64 keys on
 // the GPU (shuffle/mod.rs:163-188). Used by bench.py's RCCL exchange leg to
@@ -4384,229 +3514,6 @@ void auron_repartition_free(int64_t handle) {
 }
 
 }  // extern "C"
-
-// test-only introspection: decode a TaskDefinition and render a one-line
-// summary (verifies the hand-rolled proto reader against encoders)
-int32_t auron_debug_decode_plan(const uint8_t* data, size_t len, char* out,
-                                size_t out_cap) {
-  std::string err;
-  auto td = decode_task_definition(data, len, &err);
-  std::string s;
-  if (!td) {
-    s = "ERROR: " + err;
-  } else {
-    s = "task stage=" + std::to_string(td->stage_id) +
-        " part=" + std::to_string(td->partition_id) +
-        " tid=" + std::to_string(td->task_id) + " plan=";
-    const PlanNode* p = td->plan.get();
-    while (p) {
-      switch (p->kind) {
-        case PlanNode::ShuffleWriter: {
-          const auto& sw = *p->shuffle_writer;
-          s += "ShuffleWriter(kind=" + std::to_string((int)sw.partitioning.kind) +
-               ",P=" + std::to_string(sw.partitioning.partition_count) +
-               ",nhash=" + std::to_string(sw.partitioning.hash_exprs.size()) +
-               ",data=" + sw.output_data_file + ")->";
-          p = sw.input.get();
-          break;
-        }
-        case PlanNode::Agg: {
-          const auto& ag = *p->agg;
-          s += "Agg(mode=" +
-               std::to_string(ag.modes.empty() ? -1 : (int)ag.modes[0]) +
-               ",ngroup=" + std::to_string(ag.grouping_exprs.size()) +
-               ",nagg=" + std::to_string(ag.agg_exprs.size());
-          for (const auto& e : ag.agg_exprs)
-            s += ",fn" + std::to_string(e.agg_function) + "rt" +
-                 std::to_string((int)e.return_type);
-          s += ",skip=" + std::to_string((int)ag.supports_partial_skipping) +
-               ")->";
-          p = ag.input.get();
-          break;
-        }
-        case PlanNode::Filter: {
-          s += "Filter(npred=" +
-               std::to_string(p->filter->predicates.size()) + ")->";
-          p = p->filter->input.get();
-          break;
-        }
-        case PlanNode::Projection: {
-          s += "Project(ncols=" +
-               std::to_string(p->projection->exprs.size()) + ")->";
-          p = p->projection->input.get();
-          break;
-        }
-        case PlanNode::ParquetScan: {
-          const auto& pq = *p->parquet;
-          s += "ParquetScan(nfiles=" + std::to_string(pq.files.size()) +
-               ",nfields=" + std::to_string(pq.schema.fields.size()) +
-               ",nproj=" + std::to_string(pq.projection.size()) + ")";
-          p = nullptr;
-          break;
-        }
-        case PlanNode::IpcReader: {
-          const auto& ir = *p->ipc_reader;
-          s += "IpcReader(nfields=" + std::to_string(ir.schema.fields.size()) +
-               ",rid=" + ir.resource_id + ")";
-          p = nullptr;
-          break;
-        }
-        case PlanNode::FFIReader: {
-          const auto& fr = *p->ffi_reader;
-          s += "FFIReader(nfields=" + std::to_string(fr.schema.fields.size()) +
-               ",rid=" + fr.resource_id + ")";
-          p = nullptr;
-          break;
-        }
-      }
-    }
-  }
-  // expression trees of Filter / Projection nodes, root to leaf, appended
-  // after the chain summary
-  if (td) {
-    std::string ex;
-    const PlanNode* p = td->plan.get();
-    while (p) {
-      switch (p->kind) {
-        case PlanNode::ShuffleWriter: p = p->shuffle_writer->input.get(); break;
-        case PlanNode::Agg: p = p->agg->input.get(); break;
-        case PlanNode::Filter:
-          ex += " Filter[";
-          for (size_t i = 0; i < p->filter->predicates.size(); i++)
-            ex += (i ? "; " : "") + expr_tree_text(p->filter->predicates[i]);
-          ex += "]";
-          p = p->filter->input.get();
-          break;
-        case PlanNode::Projection:
-          ex += " Project[";
-          for (size_t i = 0; i < p->projection->exprs.size(); i++)
-            ex += (i ? "; " : "") + expr_tree_text(p->projection->exprs[i]);
-          ex += "]";
-          p = p->projection->input.get();
-          break;
-        default: p = nullptr;
-      }
-    }
-    if (!ex.empty()) s += " exprs:" + ex;
-  }
-  if (s.size() + 1 > out_cap) return -1;
-  memcpy(out, s.c_str(), s.size() + 1);
-  return (int32_t)s.size();
-}
-
-namespace auron {
-namespace {
-// Programs of a plan whose root is a Filter or a Projection directly over a
-// reader: one AND-ed mask program for a Filter, one value program per
-// non-Column expr for a Projection (Column exprs yield no program). The same
-// compile entry points the operators use.
-bool debug_compile_programs(const uint8_t* data, size_t len,
-                            std::vector<ExprProgram>* progs,
-                            std::vector<int>* expr_index, std::string* err) {
-  auto td = decode_task_definition(data, len, err);
-  if (!td) return false;
-  const PlanNode* root = td->plan.get();
-  const PlanNode* in = nullptr;
-  if (root->kind == PlanNode::Filter) in = root->filter->input.get();
-  else if (root->kind == PlanNode::Projection)
-    in = root->projection->input.get();
-  else {
-    *err = "plan root must be a Filter or a Projection";
-    return false;
-  }
-  const Schema* sc = nullptr;
-  if (in && in->kind == PlanNode::FFIReader) sc = &in->ffi_reader->schema;
-  else if (in && in->kind == PlanNode::IpcReader) sc = &in->ipc_reader->schema;
-  if (!sc) {
-    *err = "the Filter / Projection input must be an FFIReader or IpcReader";
-    return false;
-  }
-  std::vector<DType> dts;
-  for (const Field& f : sc->fields) dts.push_back(f.dtype);
-  if (root->kind == PlanNode::Filter) {
-    ExprProgram p;
-    if (!compile_filter_program(root->filter->predicates, dts, &p, err))
-      return false;
-    progs->push_back(p);
-    expr_index->push_back(0);
-    return true;
-  }
-  const auto& exprs = root->projection->exprs;
-  for (size_t i = 0; i < exprs.size(); i++) {
-    if (exprs[i].kind == Expr::Column) continue;
-    ExprProgram p;
-    if (!compile_value_program(exprs[i], dts, &p, err)) {
-      *err = "expr " + std::to_string(i) + ": " + *err;
-      return false;
-    }
-    progs->push_back(p);
-    expr_index->push_back((int)i);
-  }
-  return true;
-}
-}  // namespace
-}  // namespace auron
-
-// test-only: compile the expressions of a Filter / Projection plan and render
-// the programs, one per line; "ERROR: <cause>" on a plan-build failure.
-// Host-only: needs no GPU.
-int32_t auron_debug_compile_expr(const uint8_t* data, size_t len, char* out,
-                                 size_t out_cap) {
-  std::vector<ExprProgram> progs;
-  std::vector<int> idx;
-  std::string err, s;
-  if (!debug_compile_programs(data, len, &progs, &idx, &err)) {
-    s = "ERROR: " + err;
-  } else {
-    for (size_t i = 0; i < progs.size(); i++)
-      s += "expr" + std::to_string(idx[i]) + " " +
-           expr_program_text(progs[i]) + "\n";
-  }
-  if (s.size() + 1 > out_cap) return -1;
-  memcpy(out, s.c_str(), s.size() + 1);
-  return (int32_t)s.size();
-}
-
-// test-only: run the compiled program of expression `expr_index` (0 for a
-// Filter) on host arrays through the interpreter that shares the kernel's
-// per-row evaluator. col_values[c] holds n values at column c's width,
-// col_valid[c] one byte per row or NULL. Writes n value bit patterns and n
-// states (0 valid, 1 null, 2 poison); returns the root type code (0 Int32,
-// 1 Int64, 2 Float64, 3 Bool) or -1 with the cause in err.
-int32_t auron_debug_eval_expr(const uint8_t* data, size_t len,
-                              int32_t expr_index, int32_t ncols,
-                              const void* const* col_values,
-                              const uint8_t* const* col_valid, int64_t n,
-                              uint64_t* out_bits, uint8_t* out_state,
-                              char* err_out, size_t err_cap) {
-  std::vector<ExprProgram> progs;
-  std::vector<int> idx;
-  std::string err;
-  const ExprProgram* prog = nullptr;
-  if (debug_compile_programs(data, len, &progs, &idx, &err)) {
-    for (size_t i = 0; i < progs.size(); i++)
-      if (idx[i] == expr_index) prog = &progs[i];
-    if (!prog) err = "no computed expression at index " +
-                     std::to_string(expr_index);
-  }
-  if (prog)
-    for (int s = 0; s < prog->nslots; s++)
-      if ((int64_t)prog->slot_col[s] >= ncols || !col_values[prog->slot_col[s]]) {
-        err = "input column " + std::to_string(prog->slot_col[s]) +
-              " not supplied";
-        prog = nullptr;
-        break;
-      }
-  if (!prog) {
-    snprintf(err_out, err_cap, "%s", err.c_str());
-    return -1;
-  }
-  std::vector<ExprHostCol> cols((size_t)ncols);
-  for (int32_t c = 0; c < ncols; c++)
-    cols[c] = ExprHostCol{col_values[c], col_valid ? col_valid[c] : nullptr};
-  expr_eval_host(*prog, cols, n, out_bits, out_state);
-  return (int32_t)prog->root_ty;
-}
 
 int64_t auron_get_metric(int64_t handle, const char* name) {
   std::lock_guard<std::mutex> lk(g_mu);

@@ -138,3 +138,52 @@ def test_new_agg_families_through_shuffle_and_ipc(tmp_path):
                                   exp_nv[oi])
     np.testing.assert_array_equal(
         got["first_ignores_null"][0][gi][exp_nv[oi]], exp_n[oi][exp_nv[oi]])
+
+
+def test_ipc_read_null_key_group(tmp_path):
+    """IpcReader batches that carry a validity bitmap next to the binary
+    accumulator column: ~2 % null keys form one null-key group, whose
+    partition reads back with key validity set."""
+    P = 8
+    rng = np.random.default_rng(23)
+    n = 4_000
+    keys = rng.integers(0, 300, n).astype(np.int64)
+    vals = rng.integers(0, 1_000, n).astype(np.float64)
+    kv = rng.random(n) >= 0.02
+    vv = rng.random(n) >= 0.1
+    data_file = str(tmp_path / "n.data")
+    index_file = str(tmp_path / "n.index")
+
+    t = blaze_amd.Task(
+        plan.plan_agg_shuffle(data_file, index_file, num_partitions=P),
+        batches=[[(keys, kv), (vals, vv)]])
+    assert t.run() == []
+    t.finalize()
+
+    index = np.frombuffer(open(index_file, "rb").read(), dtype="<u8")
+    blob = open(data_file, "rb").read()
+    segments = [blob[index[p]:index[p + 1]] for p in range(P)
+                if index[p + 1] > index[p]]
+    assert len(segments) > 1
+
+    t2 = blaze_amd.Task(plan.plan_ipc_final(), ipc_segments=segments)
+    outs = t2.run()
+    got_keys = np.concatenate([ob[0]["values"] for ob in outs])
+    got_kv = np.concatenate(
+        [ob[0]["valid"] if ob[0]["valid"] is not None
+         else np.ones(len(ob[0]["values"]), bool) for ob in outs])
+    got_sums = np.concatenate([ob[1]["values"] for ob in outs])
+    got_cnts = np.concatenate([ob[2]["values"] for ob in outs])
+    t2.finalize()
+
+    orc = oracle.Agg()
+    orc.update(keys, vals, key_valid=kv, val_valid=vv)
+    ref = orc.output()
+    assert len(got_keys) == orc.num_groups
+    assert (~got_kv).sum() == 1 and (~ref["key_valid"]).sum() == 1
+    # null-key group last, the others by key
+    gi = np.lexsort((got_keys, ~got_kv))
+    oi = np.lexsort((ref["keys"], ~ref["key_valid"]))
+    np.testing.assert_array_equal(got_keys[gi][:-1], ref["keys"][oi][:-1])
+    np.testing.assert_array_equal(got_sums[gi], ref["sums"][oi])
+    np.testing.assert_array_equal(got_cnts[gi], ref["counts"][oi])

@@ -219,3 +219,44 @@ def test_parquet_gpu_page_decompress_ab(tmp_path):
         _run_and_check(ps, keys, vals, vv)
     finally:
         os.environ.pop("AURON_PARQUET_GPUCOMP", None)
+
+
+@pytest.fixture(scope="module")
+def branch_files(tmp_path_factory):
+    """3500 rows in row groups of 1003/1003/1003/491 (none a multiple of 8 or
+    64). val validity per group: none null / ~30 % null / ~30 % null / only
+    the last 5 rows null. Written once with and once without dictionary."""
+    rng = np.random.default_rng(57)
+    n, rgs = 3500, 1003
+    keys = rng.integers(0, 300, n).astype(np.int64)
+    vals = rng.integers(0, 1000, n).astype(np.float64)
+    vv = np.ones(n, bool)
+    vv[rgs:3 * rgs] = rng.random(2 * rgs) >= 0.3
+    vv[-5:] = False
+    d = tmp_path_factory.mktemp("branches")
+    files = {dictionary: _write(d, f"b_{dictionary}.parquet", keys, vals, vv,
+                                "snappy", dictionary, row_group_size=rgs)
+             for dictionary in (True, False)}
+    assert pq.ParquetFile(files[True][0]).metadata.num_row_groups == 4
+    return files, keys, vals, vv
+
+
+@pytest.mark.parametrize("win", [None, "1"])
+@pytest.mark.parametrize("knob", [None, "AURON_PARQUET_GPUCOMP",
+                                  "AURON_PARQUET_GPU"])
+@pytest.mark.parametrize("dictionary", [True, False])
+def test_parquet_assembly_branches(branch_files, monkeypatch, dictionary,
+                                   knob, win):
+    """Every chunk-assembly branch of the scan at a small size: device page
+    decompression, device def-level / dictionary-index expansion and the
+    host-decoded paths, each with and without nulls in the chunk, in one
+    window and in one window per row group."""
+    files, keys, vals, vv = branch_files
+    for k in ("AURON_PARQUET_GPUCOMP", "AURON_PARQUET_GPU",
+              "AURON_PARQUET_WIN"):
+        monkeypatch.delenv(k, raising=False)
+    if knob:
+        monkeypatch.setenv(knob, "0")
+    if win:
+        monkeypatch.setenv("AURON_PARQUET_WIN", win)
+    _run_and_check(files[dictionary], keys, vals, vv)
