@@ -86,6 +86,7 @@ class PinnedPool {
     if (it != free_.end() && !it->second.empty()) {
       void* p = it->second.back();
       it->second.pop_back();
+      cached_ -= size;
       return p;
     }
     return nullptr;
@@ -195,6 +196,86 @@ class PinnedBuf {
  private:
   void* ptr_ = nullptr;
   size_t size_ = 0;
+};
+
+// Owning, move-only host byte buffer for exported columns (values, validity
+// bitmaps, offsets). Pinned and pool-backed, so a D2H copy lands straight in
+// the memory that is handed to the consumer; the Arrow release callback gives
+// it back to the pool. Capacities are rounded up so that output batches of
+// varying length share pool entries: to a power of two up to 1 MiB (4 KiB at
+// least), to a whole MiB above, which keeps the pinned excess of a large
+// column below 1 MiB.
+class HostBuf {
+ public:
+  HostBuf() = default;
+  explicit HostBuf(size_t size) { alloc(size); }
+  HostBuf(const HostBuf&) = delete;
+  HostBuf& operator=(const HostBuf&) = delete;
+  HostBuf(HostBuf&& o) noexcept : ptr_(o.ptr_), size_(o.size_), cap_(o.cap_) {
+    o.ptr_ = nullptr;
+    o.size_ = o.cap_ = 0;
+  }
+  HostBuf& operator=(HostBuf&& o) noexcept {
+    if (this != &o) {
+      free();
+      ptr_ = o.ptr_;
+      size_ = o.size_;
+      cap_ = o.cap_;
+      o.ptr_ = nullptr;
+      o.size_ = o.cap_ = 0;
+    }
+    return *this;
+  }
+  ~HostBuf() { free(); }
+
+  // size 0 still allocates: an exported Arrow buffer pointer must not be null
+  void alloc(size_t size) {
+    free();
+    constexpr size_t MIB = (size_t)1 << 20;
+    size_t cap = 4096;
+    while (cap < size && cap < MIB) cap <<= 1;
+    if (cap < size) cap = (size + MIB - 1) / MIB * MIB;
+    ptr_ = PinnedPool::inst().get(cap);
+    if (!ptr_) AURON_HIP(hipHostMalloc(&ptr_, cap));
+    size_ = size;
+    cap_ = cap;
+  }
+  void free() {
+    if (ptr_) give_back(ptr_, cap_);
+    ptr_ = nullptr;
+    size_ = cap_ = 0;
+  }
+  // hand the allocation to another owner, who returns it with give_back()
+  void* release(size_t* cap) {
+    *cap = cap_;
+    size_ = cap_ = 0;
+    return std::exchange(ptr_, nullptr);
+  }
+  static void give_back(void* p, size_t cap) {
+    if (!PinnedPool::inst().put(p, cap)) (void)hipHostFree(p);
+  }
+  // the one place a host copy of column payload is made (two output columns
+  // over one source); *copied is the caller's byte counter
+  HostBuf clone(int64_t* copied) const {
+    HostBuf c;
+    if (!ptr_) return c;
+    c.alloc(size_);
+    memcpy(c.ptr_, ptr_, size_);
+    *copied += (int64_t)size_;
+    return c;
+  }
+
+  template <typename T = uint8_t>
+  T* as() const {
+    return static_cast<T*>(ptr_);
+  }
+  uint8_t* data() const { return static_cast<uint8_t*>(ptr_); }
+  size_t size() const { return size_; }
+  bool empty() const { return ptr_ == nullptr; }
+
+ private:
+  void* ptr_ = nullptr;
+  size_t size_ = 0, cap_ = 0;
 };
 
 // Double-buffered pinned upload: hipMemcpyAsync from PAGEABLE memory blocks

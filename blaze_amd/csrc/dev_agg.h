@@ -66,17 +66,38 @@ __device__ __forceinline__ uint64_t mix64(uint64_t x) {
   return x ^ (x >> 31);
 }
 
+// add v to *counter with ONE atomic per wave. Every lane of the wave must
+// reach the call (converged control flow, 1-D block of whole waves); lanes
+// with nothing to add pass 0.
+__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+  return v;
+}
+__device__ __forceinline__ void wave_add_u32(uint32_t* counter, uint32_t v) {
+  v = wave_sum_u32(v);
+  if ((threadIdx.x & 63) == 0 && v) atomicAdd(counter, v);
+}
+// null count of one freshly built validity byte covering rows [i, n)
+__device__ __forceinline__ uint32_t byte_nulls(uint8_t bm, int64_t i,
+                                               int64_t n) {
+  int nb = n - i < 8 ? (int)(n - i) : 8;
+  return (uint32_t)(nb - __popc((uint32_t)bm));
+}
+
 // probe-or-insert; returns acc index (slot, or cap/cap+1 for the special
 // groups), or -1 when the probe exhausts the table (table full / corrupt) —
 // the caller skips the row and the host fails the task loudly via the error
 // flag. The probe is a BOUNDED loop: an unbounded no-side-effect loop
 // iteration is UB under C++ forward-progress rules and may be miscompiled.
-__device__ __forceinline__ int64_t agg_upsert_slot(const AggTable t, int64_t key,
-                                                   bool key_null) {
+// A newly claimed group is counted in the caller's register *new_groups;
+// the kernel publishes the sum once at its end (agg_publish_new_groups).
+// Nothing on the device reads t.num_groups, and the host reads it only after
+// a stream sync, so the counter needs to be right at kernel boundaries only.
+__device__ __forceinline__ int64_t agg_upsert_slot_counted(
+    const AggTable t, int64_t key, bool key_null, uint32_t* new_groups) {
   if (key_null || key == KEY_EMPTY) {
     int which = key_null ? 1 : 0;
-    if (atomicCAS(&t.special_used[which], 0u, 1u) == 0u)
-      atomicAdd(t.num_groups, 1ull);
+    if (atomicCAS(&t.special_used[which], 0u, 1u) == 0u) (*new_groups)++;
     return t.cap + which;
   }
   uint64_t h = mix64((uint64_t)key);
@@ -90,7 +111,7 @@ __device__ __forceinline__ int64_t agg_upsert_slot(const AggTable t, int64_t key
                                             (unsigned long long)KEY_EMPTY,
                                             (unsigned long long)key);
       if (prev == KEY_EMPTY) {
-        atomicAdd(t.num_groups, 1ull);
+        (*new_groups)++;
         return i;
       }
       if (prev == key) return i;
@@ -99,6 +120,23 @@ __device__ __forceinline__ int64_t agg_upsert_slot(const AggTable t, int64_t key
   }
   atomicOr(t.error_flag, 1u);
   return -1;
+}
+
+// kernel end, every lane: one t.num_groups update per wave
+__device__ __forceinline__ void agg_publish_new_groups(const AggTable t,
+                                                       uint32_t new_groups) {
+  new_groups = wave_sum_u32(new_groups);
+  if ((threadIdx.x & 63) == 0 && new_groups)
+    atomicAdd(t.num_groups, (unsigned long long)new_groups);
+}
+
+// uncounted form: publishes each new group at once
+__device__ __forceinline__ int64_t agg_upsert_slot(const AggTable t, int64_t key,
+                                                   bool key_null) {
+  uint32_t fresh = 0;
+  int64_t a = agg_upsert_slot_counted(t, key, key_null, &fresh);
+  if (fresh) atomicAdd(t.num_groups, 1ull);
+  return a;
 }
 
 // order-preserving f64 <-> u64 map: monotone, so u64 atomicMin/atomicMax

@@ -136,7 +136,8 @@ DevBatch import_batch(const ArrowArray* a, const ArrowSchema* schema,
 
 // ------------------------------------------------------------ arrow export --
 struct ExportPriv {
-  std::vector<void*> host_bufs;
+  // pool-backed host buffers taken over from the HostOutCols: (ptr, capacity)
+  std::vector<std::pair<void*, size_t>> host_bufs;
   std::vector<const void*> buffer_ptrs;
   std::vector<ArrowArray> children_store;
   std::vector<ArrowArray*> children_ptrs;
@@ -150,7 +151,7 @@ struct ExportPriv {
 void release_exported_array(ArrowArray* a) {
   if (!a || !a->release) return;
   ExportPriv* p = (ExportPriv*)a->private_data;
-  for (void* b : p->host_bufs) free(b);
+  for (auto& b : p->host_bufs) HostBuf::give_back(b.first, b.second);
   delete p;
   a->release = nullptr;
 }
@@ -218,11 +219,19 @@ void export_schema(const std::vector<OutField>& fields, ArrowSchema* out) {
 
 // host-side column staging for export
 struct HostOutCol {
-  DType dt;                       // list cols: the ITEM type
-  std::vector<uint8_t> values;    // list cols: child (item) values
-  std::vector<uint8_t> validity;  // empty = no nulls
-  std::vector<int32_t> offsets;   // binary / list: n+1
+  DType dt;            // list cols: the ITEM type
+  HostBuf values;      // list cols: child (item) values
+  HostBuf validity;    // empty = no nulls
+  HostBuf offsets;     // binary / list: (n+1) int32
+  int64_t null_count = 0;  // exact; validity is attached only when > 0
   bool is_list = false;
+  // emit bookkeeping, resolved at the batch's one sync (AggOp::emit_end):
+  // the device null counter that belongs to `validity`, and the column of
+  // the same batch whose values(+offsets) / validity this one duplicates
+  int null_slot = -1;
+  int values_from = -1, validity_from = -1;
+
+  const int32_t* offs() const { return offsets.as<int32_t>(); }
 };
 
 // device-resident column staging: partial-agg output that stays in HBM and
@@ -251,32 +260,28 @@ void export_batch(int64_t num_rows, std::vector<HostOutCol>&& cols,
     memset(&ch, 0, sizeof(ch));
     ch.length = num_rows;
     ch.offset = 0;
-    auto copy_out = [&](const void* src, size_t len) -> void* {
-      void* b = malloc(len ? len : 1);
-      memcpy(b, src, len);
-      priv->host_bufs.push_back(b);
+    // the export takes the buffers over; release_exported_array returns
+    // them to the pool
+    auto take = [&](HostBuf& hb) -> const void* {
+      if (hb.empty()) hb.alloc(0);  // Arrow data buffers are never null
+      size_t cap = 0;
+      void* b = hb.release(&cap);
+      priv->host_bufs.push_back({b, cap});
       return b;
     };
     std::vector<const void*>& bufs = priv->child_buffer_ptrs[i];
     const void* validity = nullptr;
-    if (!c.validity.empty()) {
-      validity = copy_out(c.validity.data(), c.validity.size());
-      int64_t nulls = 0;
-      for (int64_t r = 0; r < num_rows; r++)
-        if (!((c.validity[r >> 3] >> (r & 7)) & 1)) nulls++;
-      ch.null_count = nulls;
-    } else {
-      ch.null_count = 0;
-    }
+    if (!c.validity.empty() && c.null_count > 0) validity = take(c.validity);
+    ch.null_count = validity ? c.null_count : 0;
     if (c.is_list) {
       // list<prim>: parent {validity, offsets}; child = item values
-      bufs = {validity, copy_out(c.offsets.data(), c.offsets.size() * 4)};
       ArrowArray& it = priv->item_store[i];
       memset(&it, 0, sizeof(it));
-      it.length = c.offsets.empty() ? 0 : c.offsets.back();
+      it.length = c.offsets.empty() ? 0 : c.offs()[num_rows];
       it.null_count = 0;
+      bufs = {validity, take(c.offsets)};
       std::vector<const void*>& ibufs = priv->item_buffer_ptrs[i];
-      ibufs = {nullptr, copy_out(c.values.data(), c.values.size())};
+      ibufs = {nullptr, take(c.values)};
       it.n_buffers = 2;
       it.buffers = ibufs.data();
       it.release = [](ArrowArray* a) { a->release = nullptr; };
@@ -284,10 +289,10 @@ void export_batch(int64_t num_rows, std::vector<HostOutCol>&& cols,
       ch.n_children = 1;
       ch.children = &priv->item_ptrs[i];
     } else if (c.dt == DType::Binary || c.dt == DType::Utf8) {
-      bufs = {validity, copy_out(c.offsets.data(), c.offsets.size() * 4),
-              copy_out(c.values.data(), c.values.size())};
+      const void* offs = take(c.offsets);
+      bufs = {validity, offs, take(c.values)};
     } else {
-      bufs = {validity, copy_out(c.values.data(), c.values.size())};
+      bufs = {validity, take(c.values)};
     }
     ch.n_buffers = (int64_t)bufs.size();
     ch.buffers = bufs.data();
@@ -307,14 +312,15 @@ void export_batch(int64_t num_rows, std::vector<HostOutCol>&& cols,
 }
 
 // Variable-width output layout: device lens[n] (int32) -> host exclusive scan
-// -> the n+1 offsets, uploaded to d_offs and returned (the caller keeps the
-// vector alive until its next sync: it is the source of the upload). Arrow
-// offsets are int32, so a total past INT32_MAX fails instead of wrapping.
-std::vector<int32_t> lens_to_offsets(const void* d_lens, int64_t n,
-                                     int32_t* d_offs, hipStream_t stream) {
-  std::vector<int32_t> offs(n + 1, 0);
-  AURON_HIP(hipMemcpyAsync(offs.data() + 1, d_lens, n * 4,
-                           hipMemcpyDeviceToHost, stream));
+// -> the n+1 offsets in the caller's offs[], uploaded to d_offs (the caller
+// keeps offs alive until its next sync: it is the source of the upload).
+// Arrow offsets are int32, so a total past INT32_MAX fails instead of
+// wrapping.
+void lens_to_offsets_into(const void* d_lens, int64_t n, int32_t* offs,
+                          int32_t* d_offs, hipStream_t stream) {
+  offs[0] = 0;
+  AURON_HIP(hipMemcpyAsync(offs + 1, d_lens, n * 4, hipMemcpyDeviceToHost,
+                           stream));
   AURON_HIP(hipStreamSynchronize(stream));
   int64_t total = 0;
   for (int64_t i = 0; i < n; i++) {
@@ -323,8 +329,14 @@ std::vector<int32_t> lens_to_offsets(const void* d_lens, int64_t n,
       FAIL("variable-width output exceeds 2 GiB in one batch (int32 offsets)");
     offs[i + 1] = (int32_t)total;
   }
-  AURON_HIP(hipMemcpyAsync(d_offs, offs.data(), (n + 1) * 4,
-                           hipMemcpyHostToDevice, stream));
+  AURON_HIP(hipMemcpyAsync(d_offs, offs, (n + 1) * 4, hipMemcpyHostToDevice,
+                           stream));
+}
+
+std::vector<int32_t> lens_to_offsets(const void* d_lens, int64_t n,
+                                     int32_t* d_offs, hipStream_t stream) {
+  std::vector<int32_t> offs(n + 1, 0);
+  lens_to_offsets_into(d_lens, n, offs.data(), d_offs, stream);
   return offs;
 }
 
@@ -1083,7 +1095,8 @@ class AggOp {
     launch_agg_gather_out(t_, order_slots, n, keys.get<int64_t>(),
                           kc.validity.get<uint8_t>(), sums.get<double>(),
                           svalid.get<uint8_t>(), cnts.get<long long>(),
-                          nullptr, nullptr, nullptr, nullptr, stream_);
+                          nullptr, nullptr, nullptr, nullptr, nullptr,
+                          stream_);
     narrow_keys(keys, wide, n);
     kc.values = std::move(keys);
     // freeze lens -> device exclusive scan -> offsets (+ total in slot n)
@@ -1467,6 +1480,9 @@ class AggOp {
     const uint8_t* kv = key.validity ? key.validity + done / 8 : nullptr;
     const uint8_t* vv = val.validity ? val.validity + done / 8 : nullptr;
     const int64_t mat = (int64_t)AGG3_NBUCK << AGG3_GRID_LOG2;
+    // the merges below insert rows of this chunk and may spill (table_order)
+    // before the caller advances row_cursor_
+    first_row_bound_ = row_cursor_ + (uint64_t)chunk;
 
     if (!d_partkv_) {
       // 24B records + one line of alignment padding per (block,bucket)
@@ -1495,19 +1511,28 @@ class AggOp {
     // store (key - base) u32 — 33% less partition traffic. Out-of-range keys
     // in later chunks take the counted leftover bypass, so the choice is a
     // pure optimization, never a correctness bet.
-    if (agg2_p16_en_ && !p16_decided_) {
-      // one-time key-range probe (8 B/row) so even the FIRST chunk runs
-      // the packed layout; ~0.35 ms vs ~2.8 ms saved on a 256M chunk
+    // The range comes out of the first chunk's histogram pass (one
+    // atomicMin/atomicMax per wave), so even the FIRST chunk runs the packed
+    // layout and no pass over the keys is spent on the decision.
+    const bool probe = agg2_p16_en_ && !p16_decided_;
+    if (probe) {
       if (!d_kminmax_) d_kminmax_.alloc(16);
       AURON_HIP(hipMemsetAsync(d_kminmax_.get(), 0xFF, 8, stream_));
       AURON_HIP(hipMemsetAsync(d_kminmax_.get<uint8_t>() + 8, 0, 8, stream_));
-      launch_keys_minmax(keys, kv, chunk,
-                         d_kminmax_.get<unsigned long long>(), stream_);
-      uint64_t h_kmm[2];
+    }
+    launch_agg2_hist(keys, kv, chunk, AGG3_NBUCK_LOG2, AGG3_GRID_LOG2,
+                     d_counts_.get<uint32_t>(),
+                     (uint32_t*)(d_counters_.get<uint8_t>() + 16),
+                     probe ? d_kminmax_.get<unsigned long long>() : nullptr,
+                     stream_);
+    if (probe) {
+      // pinned_agg2_'s four words are free until the counter readback below
+      uint64_t* h_kmm = pinned_agg2_.get<uint64_t>();
       AURON_HIP(hipMemcpyAsync(h_kmm, d_kminmax_.get(), 16,
                                hipMemcpyDeviceToHost, stream_));
       AURON_HIP(hipStreamSynchronize(stream_));
       p16_decided_ = true;
+      // an empty range (no normal key in the chunk) reads ~0 > 0: stays 24B
       if (h_kmm[0] <= h_kmm[1] && h_kmm[1] - h_kmm[0] <= 0xFFFFFFFFull) {
         packed16_ = true;
         key_base16_ = (int64_t)(h_kmm[0] ^ 0x8000000000000000ull);
@@ -1516,9 +1541,6 @@ class AggOp {
       }
     }
     const int rec = packed16_ ? 16 : 24;
-    launch_agg2_hist(keys, kv, chunk, AGG3_NBUCK_LOG2, AGG3_GRID_LOG2,
-                     d_counts_.get<uint32_t>(),
-                     (uint32_t*)(d_counters_.get<uint8_t>() + 16), stream_);
     launch_agg3_line_sizes(d_counts_.get<uint32_t>(), mat + 1,
                            d_linesz_.get<uint32_t>(), rec, stream_);
     size_t tb = d_scan_tmp_.size();
@@ -1595,17 +1617,25 @@ class AggOp {
     AURON_HIP(hipMemsetAsync(dcount.get(), 0, 8, stream_));
     launch_agg_compact(t_, slots_u.get<uint32_t>(),
                        first.get<unsigned long long>(),
-                       dcount.get<unsigned long long>(), stream_);
+                       dcount.get<unsigned long long>(), (int64_t)ng, stream_);
+    // every first_row is the global index of a consumed row or record
+    // (spilled groups keep theirs from before the spill), so all of them are
+    // below row_cursor_ — or, when a two-phase chunk spills while it merges,
+    // below that chunk's end, which row_cursor_ reaches only afterwards:
+    // sort only the bits that can be set
+    const uint64_t bound = std::max(row_cursor_, first_row_bound_);
+    int end_bit = 1;
+    while (end_bit < 64 && (bound >> end_bit) != 0) end_bit++;
     size_t tmp_bytes = 0;
     sort_pairs_u64_u32(first.get<unsigned long long>(), slots_u.get<uint32_t>(),
                        first_sorted->get<unsigned long long>(),
                        slots_sorted->get<uint32_t>(), (int64_t)ng, nullptr,
-                       &tmp_bytes, stream_);
+                       &tmp_bytes, stream_, end_bit);
     DevBuf tmp(tmp_bytes);
     sort_pairs_u64_u32(first.get<unsigned long long>(), slots_u.get<uint32_t>(),
                        first_sorted->get<unsigned long long>(),
                        slots_sorted->get<uint32_t>(), (int64_t)ng, tmp.get(),
-                       &tmp_bytes, stream_);
+                       &tmp_bytes, stream_, end_bit);
     // pooled buffers (slots_u/first/tmp) must not be recycled while the sort
     // still reads them — the pool, unlike hipFree, does not synchronize
     AURON_HIP(hipStreamSynchronize(stream_));
@@ -1649,20 +1679,22 @@ class AggOp {
       launch_agg_gather_out(t_, d_order.get<uint32_t>(), n,
                             keys.get<int64_t>(), nullptr, nullptr, nullptr,
                             nullptr, nullptr, nullptr, nullptr, nullptr,
-                            stream_);
+                            nullptr, stream_);
       std::vector<int64_t> h_keys(n);
       AURON_HIP(hipMemcpyAsync(h_keys.data(), keys.get(), n * 8,
                                hipMemcpyDeviceToHost, stream_));
-      HostOutCol rec = freeze_agg_buf(d_order.get<uint32_t>(), n);  // syncs
+      HostOutCol rec = freeze_agg_buf(d_order.get<uint32_t>(), n);
+      emit_sync();  // h_keys and the frozen bytes are on the host
+      const int32_t* rec_offs = rec.offs();
       if (spill_.empty()) spill_.resize(num_spill_buckets_);
       for (int64_t i = 0; i < n; i++) {
         SpillBucket& b =
             spill_[host_mix64((uint64_t)h_keys[i]) % num_spill_buckets_];
         b.keys.push_back(h_keys[i]);
         b.first_rows.push_back(main_first[i]);
-        b.lens.push_back(rec.offsets[i + 1] - rec.offsets[i]);
-        b.data.insert(b.data.end(), rec.values.begin() + rec.offsets[i],
-                      rec.values.begin() + rec.offsets[i + 1]);
+        b.lens.push_back(rec_offs[i + 1] - rec_offs[i]);
+        b.data.insert(b.data.end(), rec.values.data() + rec_offs[i],
+                      rec.values.data() + rec_offs[i + 1]);
       }
       spill_count_++;
     }
@@ -1811,29 +1843,98 @@ class AggOp {
     }
   }
 
-  // D2H through a reusable pinned staging buffer (pageable D2H costs ms on
-  // this stack); dst vector is filled from the pinned copy
-  void d2h_pinned(const void* dev, std::vector<uint8_t>* dst, size_t len) {
-    if (pinned_emit_.size() < len) pinned_emit_.alloc(len);
-    AURON_HIP(hipMemcpyAsync(pinned_emit_.get(), dev, len,
-                             hipMemcpyDeviceToHost, stream_));
-    AURON_HIP(hipStreamSynchronize(stream_));
-    dst->resize(len);
-    memcpy(dst->data(), pinned_emit_.get(), len);
+  // ---- host emit -----------------------------------------------------------
+  // One output batch = emit_begin(), any number of d2h() / col_validity()
+  // enqueues straight into the columns' own export buffers, emit_end(): the
+  // batch's ONE stream sync, after which the device null counters decide
+  // which bitmaps stay attached. emit_d2h_bytes_ counts the column payload
+  // (values, bitmaps, offsets) copied down; the 4-byte counters are not
+  // payload.
+  static constexpr int EMIT_NULL_SLOTS = 256;
+
+  void emit_begin() {
+    if (!d_emit_nulls_) {
+      d_emit_nulls_.alloc(EMIT_NULL_SLOTS * 4);
+      pinned_nulls_.alloc(EMIT_NULL_SLOTS * 4);
+    }
+    AURON_HIP(hipMemsetAsync(d_emit_nulls_.get(), 0, EMIT_NULL_SLOTS * 4,
+                             stream_));
+    emit_null_used_ = 0;
   }
 
-  // validity bitmap of n rows to the host (synced)
-  std::vector<uint8_t> d2h_bitmap(const void* dev, int64_t n) {
-    std::vector<uint8_t> bm((n + 7) / 8);
-    AURON_HIP(hipMemcpyAsync(bm.data(), dev, bm.size(), hipMemcpyDeviceToHost,
+  // reserve k consecutive device null counters; returns the first index
+  int null_slots(int k) {
+    if (emit_null_used_ + k > EMIT_NULL_SLOTS)
+      FAIL("too many nullable output columns in one batch");
+    int at = emit_null_used_;
+    emit_null_used_ += k;
+    return at;
+  }
+  uint32_t* null_ctr(int slot) {
+    return d_emit_nulls_.get<uint32_t>() + slot;
+  }
+
+  // enqueue dev -> a fresh export buffer (no sync)
+  void d2h(HostBuf* dst, const void* dev, size_t len) {
+    dst->alloc(len);
+    if (len == 0) return;
+    AURON_HIP(hipMemcpyAsync(dst->data(), dev, len, hipMemcpyDeviceToHost,
                              stream_));
+    emit_d2h_bytes_ += (int64_t)len;
+  }
+
+  // bitmap of n rows whose nulls a kernel adds to counter `slot`
+  void col_validity(HostOutCol* col, const void* dev_bm, int64_t n, int slot) {
+    d2h(&col->validity, dev_bm, (size_t)(n + 7) / 8);
+    col->null_slot = slot;
+  }
+
+  // D2H sources live until the batch's sync: the device pool hands a freed
+  // buffer to whoever asks next and does not synchronize
+  void keep(DevBuf&& b) { emit_keep_.push_back(std::move(b)); }
+
+  void emit_sync() {
     AURON_HIP(hipStreamSynchronize(stream_));
-    return bm;
+    emit_keep_.clear();
+  }
+
+  // The one sync of an output batch. Keeps the rule of the Arrow null_count
+  // convention (and batch_serde's has_null header): validity is attached only
+  // when nulls exist. Columns that duplicate another column's source are
+  // cloned here, the only host copy of the emit path.
+  void emit_end(std::vector<HostOutCol>* cols) {
+    uint32_t* h_nulls = pinned_nulls_.get<uint32_t>();
+    if (emit_null_used_)
+      AURON_HIP(hipMemcpyAsync(h_nulls, d_emit_nulls_.get(),
+                               (size_t)emit_null_used_ * 4,
+                               hipMemcpyDeviceToHost, stream_));
+    emit_sync();
+    for (HostOutCol& c : *cols) {
+      if (c.null_slot < 0) continue;
+      c.null_count = (int64_t)h_nulls[c.null_slot];
+      if (c.null_count == 0) c.validity.free();
+      c.null_slot = -1;
+    }
+    for (HostOutCol& c : *cols) {
+      if (c.values_from >= 0) {
+        const HostOutCol& src = (*cols)[c.values_from];
+        c.values = src.values.clone(&emit_host_copy_bytes_);
+        c.offsets = src.offsets.clone(&emit_host_copy_bytes_);
+        c.values_from = -1;
+      }
+      if (c.validity_from >= 0) {
+        const HostOutCol& src = (*cols)[c.validity_from];
+        c.validity = src.validity.clone(&emit_host_copy_bytes_);
+        c.null_count = src.null_count;
+        c.validity_from = -1;
+      }
+    }
   }
 
   // Variable-width (Binary) column of n rows from a pair of kernels:
   // write_lens(int32_t* lens) sizes each row, write_bytes(const int32_t* offs,
-  // uint8_t* data) fills the rows at the scanned offsets.
+  // uint8_t* data) fills the rows at the scanned offsets. The data bytes are
+  // on the host after the caller's next sync.
   template <class LensFn, class BytesFn>
   HostOutCol freeze_binary_col(int64_t n, LensFn write_lens,
                                BytesFn write_bytes) {
@@ -1841,11 +1942,17 @@ class AggOp {
     col.dt = DType::Binary;
     DevBuf lens(n * 4), offs((n + 1) * 4);
     write_lens(lens.get<int32_t>());
-    col.offsets = lens_to_offsets(lens.get(), n, offs.get<int32_t>(), stream_);
-    size_t total = (size_t)col.offsets[n];
+    col.offsets.alloc((size_t)(n + 1) * 4);
+    lens_to_offsets_into(lens.get(), n, col.offsets.as<int32_t>(),
+                         offs.get<int32_t>(), stream_);
+    emit_d2h_bytes_ += n * 4;
+    size_t total = (size_t)col.offs()[n];
     DevBuf data(total ? total : 1);
     write_bytes(offs.get<int32_t>(), data.get<uint8_t>());
-    d2h_pinned(data.get(), &col.values, total);
+    d2h(&col.values, data.get(), total);
+    keep(std::move(lens));
+    keep(std::move(offs));
+    keep(std::move(data));
     return col;
   }
 
@@ -1871,8 +1978,11 @@ class AggOp {
     col.is_list = true;
     DevBuf cnts(n * 4), d_off((n + 1) * 4);
     launch_coll_counts(tv, order_slots, n, cnts.get<int32_t>(), stream_);
-    col.offsets = lens_to_offsets(cnts.get(), n, d_off.get<int32_t>(), stream_);
-    int64_t m = col.offsets[n];
+    col.offsets.alloc((size_t)(n + 1) * 4);
+    lens_to_offsets_into(cnts.get(), n, col.offsets.as<int32_t>(),
+                         d_off.get<int32_t>(), stream_);
+    emit_d2h_bytes_ += n * 4;
+    int64_t m = col.offs()[n];
     DevBuf items(m * 8 + 8);
     launch_coll_gather(tv, order_slots, n, d_off.get<int32_t>(),
                        items.get<unsigned long long>(), stream_);
@@ -1880,10 +1990,14 @@ class AggOp {
       DevBuf narrow(m * 4 + 4);
       launch_narrow_i64_i32(items.get<int64_t>(), m, narrow.get<int32_t>(),
                             stream_);
-      d2h_pinned(narrow.get(), &col.values, (size_t)m * 4);
+      d2h(&col.values, narrow.get(), (size_t)m * 4);
+      keep(std::move(narrow));
     } else {
-      d2h_pinned(items.get(), &col.values, (size_t)m * 8);
+      d2h(&col.values, items.get(), (size_t)m * 8);
     }
+    keep(std::move(cnts));
+    keep(std::move(d_off));
+    keep(std::move(items));
     return col;
   }
 
@@ -1911,6 +2025,7 @@ class AggOp {
       HostOutCol c;
       DType dt = key_dts_[k];
       DevBuf bmbuf(bm);
+      const int slot = null_slots(1);
       if (dt == DType::Utf8 || dt == DType::Binary) {
         c = freeze_binary_col(
             n,
@@ -1918,7 +2033,7 @@ class AggOp {
               launch_gkey_out_lens(g_, order_slots, n, d_gkdts_.get<uint8_t>(),
                                    (int)key_cols_.size(), (int)k,
                                    (uint32_t*)lens, bmbuf.get<uint8_t>(),
-                                   stream_);
+                                   null_ctr(slot), stream_);
             },
             [&](const int32_t* offs, uint8_t* data) {
               launch_gkey_out_bytes(g_, order_slots, n,
@@ -1932,11 +2047,13 @@ class AggOp {
         launch_gkey_out_fixed(g_, order_slots, n, d_gkdts_.get<uint8_t>(),
                               (int)key_cols_.size(), (int)k,
                               vals.get<uint8_t>(), bmbuf.get<uint8_t>(),
-                              stream_);
-        d2h_pinned(vals.get(), &c.values, n * w);
+                              null_ctr(slot), stream_);
+        d2h(&c.values, vals.get(), n * w);
+        keep(std::move(vals));
       }
       c.dt = dt;
-      attach_validity(&c, d2h_bitmap(bmbuf.get(), n), n);
+      col_validity(&c, bmbuf.get(), n, slot);
+      keep(std::move(bmbuf));
       out.push_back(std::move(c));
     }
     return out;
@@ -1979,15 +2096,18 @@ class AggOp {
       HostOutCol ac;
       int w = (ag.kind == AGGL_CNT) ? 8 : (ag.acc_t == 2 ? 4 : 8);
       DevBuf vals(n * w), bmbuf(bm);
+      // COUNT is never null: its bitmap is built but not exported
+      const int slot = (ag.kind != AGGL_CNT) ? null_slots(1) : -1;
       launch_ma_gather_out(ma_desc_, ma_, j, order_slots, n,
                            vals.get<uint8_t>(), bmbuf.get<uint8_t>(),
-                           stream_);
+                           slot >= 0 ? null_ctr(slot) : nullptr, stream_);
       ac.dt = (ag.kind == AGGL_CNT) ? DType::Int64
               : (ag.kind == AGGL_AVG) ? DType::Float64
                                       : ma_out_dt(j);
-      d2h_pinned(vals.get(), &ac.values, (size_t)n * w);
-      if (ag.kind != AGGL_CNT)
-        attach_validity(&ac, d2h_bitmap(bmbuf.get(), n), n);
+      d2h(&ac.values, vals.get(), (size_t)n * w);
+      if (slot >= 0) col_validity(&ac, bmbuf.get(), n, slot);
+      keep(std::move(vals));
+      keep(std::move(bmbuf));
       cols->push_back(std::move(ac));
     }
   }
@@ -1995,119 +2115,131 @@ class AggOp {
   std::pair<int64_t, std::vector<HostOutCol>> emit_groups(
       const uint32_t* order_slots, int64_t n) {
     DBG("agg.emit n=%lld final=%d", (long long)n, (int)final_output_);
+    emit_begin();
     std::vector<HostOutCol> cols;
     size_t bm = (n + 7) / 8;
     DevBuf keys(n * 8), kvalid(bm), sums(n * 8), svalid(bm), cnts(n * 8);
-    DevBuf mins, mvalid, maxs, xvalid;
+    DevBuf mins, mvalid, maxs, xvalid, avgs, wide, fvals[2], fvalid[2];
     if (has_mm_ && final_output_) {
       mins.alloc(n * 8);
       mvalid.alloc(bm);
       maxs.alloc(n * 8);
       xvalid.alloc(bm);
     }
+    // gather_out's counters: {key, sum, min, max} nulls
+    const int gslot = null_slots(4);
     launch_agg_gather_out(t_, order_slots, n, keys.get<int64_t>(),
                           kvalid.get<uint8_t>(), sums.get<double>(),
                           svalid.get<uint8_t>(), cnts.get<long long>(),
                           mins.get<double>(), mvalid.get<uint8_t>(),
-                          maxs.get<double>(), xvalid.get<uint8_t>(), stream_);
+                          maxs.get<double>(), xvalid.get<uint8_t>(),
+                          null_ctr(gslot), stream_);
     HostOutCol key_col;
     key_col.dt = key_out_dt();
-    DevBuf wide;
-    narrow_keys(keys, wide, n);
-    d2h_pinned(keys.get(), &key_col.values, n * dtype_width(key_col.dt));
+    if (!gkey_) {
+      narrow_keys(keys, wide, n);
+      d2h(&key_col.values, keys.get(), n * dtype_width(key_col.dt));
+      col_validity(&key_col, kvalid.get(), n, gslot);
+    }
     if (ma_mode_) {
-      attach_validity(&key_col, d2h_bitmap(kvalid.get(), n), n);
       cols.push_back(std::move(key_col));
       emit_ma_aggs(order_slots, n, &cols);
-      return {n, std::move(cols)};
-    }
-    std::vector<uint8_t> kv(bm), sv(bm);
-    AURON_HIP(hipMemcpyAsync(kv.data(), kvalid.get(), bm, hipMemcpyDeviceToHost,
-                             stream_));
-    AURON_HIP(hipMemcpyAsync(sv.data(), svalid.get(), bm, hipMemcpyDeviceToHost,
-                             stream_));
-    if (final_output_) {
-      std::vector<uint8_t> h_sums, h_cnts, h_avgs, h_mins, h_maxs;
-      std::vector<uint8_t> mv(bm), xv(bm);
-      d2h_pinned(sums.get(), &h_sums, n * 8);
-      d2h_pinned(cnts.get(), &h_cnts, n * 8);
-      bool need_avg = false;
-      for (uint32_t k : agg_kinds_) need_avg |= (k == AGGL_AVG);
-      DevBuf avgs;
-      if (need_avg) {
-        avgs.alloc(n * 8);
-        launch_avg_div(sums.get<double>(), cnts.get<long long>(), n,
-                       avgs.get<double>(), stream_);
-        d2h_pinned(avgs.get(), &h_avgs, n * 8);
-      }
-      if (has_mm_) {
-        d2h_pinned(mins.get(), &h_mins, n * 8);
-        d2h_pinned(maxs.get(), &h_maxs, n * 8);
-        AURON_HIP(hipMemcpyAsync(mv.data(), mvalid.get(), bm,
-                                 hipMemcpyDeviceToHost, stream_));
-        AURON_HIP(hipMemcpyAsync(xv.data(), xvalid.get(), bm,
-                                 hipMemcpyDeviceToHost, stream_));
-      }
-      const DType vdt = val_is_int_ ? DType::Int64 : DType::Float64;
-      HostOutCol coll_col;  // the one legacy pool serves every collect agg
-      if (has_coll_) coll_col = coll_list_col(t_, order_slots, n, vdt);
-      std::vector<uint8_t> h_firsts[2], fv[2];
-      if (has_first_) {
-        DevBuf fvals(n * 8), fvalid(bm);
-        for (int w = 0; w < 2; w++) {
-          launch_first_gather(t_, order_slots, n, w, fvals.get<double>(),
-                              fvalid.get<uint8_t>(), stream_);
-          d2h_pinned(fvals.get(), &h_firsts[w], n * 8);
-          fv[w] = d2h_bitmap(fvalid.get(), n);
-        }
-      }
-      AURON_HIP(hipStreamSynchronize(stream_));
-      DBG("agg.emit final d2h done");
+    } else if (final_output_) {
       if (gkey_) {
-        for (auto& kc2 : emit_gkey_cols(order_slots, n))
-          cols.push_back(std::move(kc2));
+        cols = emit_gkey_cols(order_slots, n);
       } else {
-        attach_validity(&key_col, kv, n);
         cols.push_back(std::move(key_col));
       }
+      const DType vdt = val_is_int_ ? DType::Int64 : DType::Float64;
+      // each source goes down once, into the first column that shows it; a
+      // later column over the same source is cloned from that one
+      int sum_at = -1, cnt_at = -1, avg_at = -1, sv_at = -1, min_at = -1,
+          max_at = -1, first_at[2] = {-1, -1}, coll_at = -1;
+      auto values_once = [&](HostOutCol* ac, int* at, const DevBuf& src) {
+        if (*at < 0) {
+          d2h(&ac->values, src.get(), n * 8);
+          *at = (int)cols.size();
+        } else {
+          ac->values_from = *at;
+        }
+      };
+      auto validity_once = [&](HostOutCol* ac, int* at, const DevBuf& src,
+                               int slot) {
+        if (*at < 0) {
+          col_validity(ac, src.get(), n, slot);
+          *at = (int)cols.size();
+        } else {
+          ac->validity_from = *at;
+        }
+      };
       for (uint32_t k : agg_kinds_) {
         HostOutCol ac;
         if (k == AGGL_CNT) {
           ac.dt = DType::Int64;
-          ac.values = h_cnts;
-        } else if (k == AGGL_MIN || k == AGGL_MAX) {
+          values_once(&ac, &cnt_at, cnts);
+        } else if (k == AGGL_MIN) {
           ac.dt = vdt;
-          ac.values = (k == AGGL_MIN) ? h_mins : h_maxs;
-          attach_validity(&ac, (k == AGGL_MIN) ? mv : xv, n);
+          int at = min_at;
+          values_once(&ac, &min_at, mins);
+          validity_once(&ac, &at, mvalid, gslot + 2);
+        } else if (k == AGGL_MAX) {
+          ac.dt = vdt;
+          int at = max_at;
+          values_once(&ac, &max_at, maxs);
+          validity_once(&ac, &at, xvalid, gslot + 3);
         } else if (k == AGGL_FIRST || k == AGGL_FIRSTIN) {
           int w = (k == AGGL_FIRSTIN) ? 1 : 0;
           ac.dt = vdt;
-          ac.values = h_firsts[w];
-          attach_validity(&ac, fv[w], n);
+          int at = first_at[w];
+          int slot = -1;
+          if (at < 0) {
+            fvals[w].alloc(n * 8);
+            fvalid[w].alloc(bm);
+            slot = null_slots(1);
+            launch_first_gather(t_, order_slots, n, w, fvals[w].get<double>(),
+                                fvalid[w].get<uint8_t>(), null_ctr(slot),
+                                stream_);
+          }
+          values_once(&ac, &first_at[w], fvals[w]);
+          validity_once(&ac, &at, fvalid[w], slot);
         } else if (k == AGGL_CLIST || k == AGGL_CSET) {
-          ac = coll_col;
+          // the one legacy pool serves every collect agg
+          if (coll_at < 0) {
+            ac = coll_list_col(t_, order_slots, n, vdt);
+            coll_at = (int)cols.size();
+          } else {
+            ac.dt = vdt;
+            ac.is_list = true;
+            ac.values_from = coll_at;
+          }
         } else if (k == AGGL_AVG) {
           ac.dt = DType::Float64;
-          ac.values = h_avgs;
-          attach_validity(&ac, sv, n);
+          if (avg_at < 0) {
+            avgs.alloc(n * 8);
+            launch_avg_div(sums.get<double>(), cnts.get<long long>(), n,
+                           avgs.get<double>(), stream_);
+          }
+          values_once(&ac, &avg_at, avgs);
+          validity_once(&ac, &sv_at, svalid, gslot + 1);
         } else {
           ac.dt = vdt;  // SUM output carries the accumulator type's raw bits
-          ac.values = h_sums;
-          attach_validity(&ac, sv, n);  // null iff cnt==0 (shared column)
+          values_once(&ac, &sum_at, sums);
+          // null iff cnt==0 (shared column)
+          validity_once(&ac, &sv_at, svalid, gslot + 1);
         }
         cols.push_back(std::move(ac));
       }
     } else {
       HostOutCol buf_col = freeze_agg_buf(order_slots, n);  // a8
-      DBG("agg.emit partial freeze d2h done");
       if (gkey_) {
         cols = emit_gkey_cols(order_slots, n);
-        cols.push_back(std::move(buf_col));
       } else {
-        attach_validity(&key_col, kv, n);
-        cols = {std::move(key_col), std::move(buf_col)};
+        cols.push_back(std::move(key_col));
       }
+      cols.push_back(std::move(buf_col));
     }
+    emit_end(&cols);
+    DBG("agg.emit d2h done");
     return {n, std::move(cols)};
   }
 
@@ -2115,6 +2247,7 @@ class AggOp {
     int64_t n = b.num_rows;
     const DevColumn& key = b.cols.at(key_col_);
     const DevColumn& val = b.cols.at(val_col_);
+    emit_begin();
     HostOutCol buf_col = freeze_binary_col(
         n,
         [&](int32_t* lens) {
@@ -2127,26 +2260,18 @@ class AggOp {
         });
     HostOutCol key_col;
     key_col.dt = key.dt;
-    d2h_pinned(key.values, &key_col.values, n * dtype_width(key.dt));
-    // pass-through keeps the input's bitmap as is (no null_count pruning)
-    if (key.validity) key_col.validity = d2h_bitmap(key.validity, n);
+    d2h(&key_col.values, key.values, n * dtype_width(key.dt));
+    // pass-through of the input's bitmap: counted, not rebuilt
+    if (key.validity) {
+      const int slot = null_slots(1);
+      launch_bitmap_null_count(key.validity, n, null_ctr(slot), stream_);
+      col_validity(&key_col, key.validity, n, slot);
+    }
     std::vector<HostOutCol> cols;
     cols.push_back(std::move(key_col));
     cols.push_back(std::move(buf_col));
+    emit_end(&cols);
     return {n, std::move(cols)};
-  }
-
-  static void attach_validity(HostOutCol* col, const std::vector<uint8_t>& bm,
-                              int64_t n) {
-    // attach only when nulls exist (Arrow null_count>0 convention, matching
-    // batch_serde has_null header semantics)
-    bool any_null = false;
-    for (int64_t i = 0; i < n; i++)
-      if (!((bm[i >> 3] >> (i & 7)) & 1)) {
-        any_null = true;
-        break;
-      }
-    if (any_null) col->validity = bm;
   }
 
  public:
@@ -2193,6 +2318,7 @@ class AggOp {
   double skip_ratio_ = 0.999;
   int64_t skip_min_rows_ = 20000;
   uint64_t row_cursor_ = 0;
+  uint64_t first_row_bound_ = 0;  // end of the two-phase chunk in flight
   uint64_t ng_bound_ = 0, ng_true_ = 0;  // conservative bound / last readback
   int64_t mem_budget_ = 8LL << 30, max_cap_ = 1 << 23;
   int num_spill_buckets_ = 16;
@@ -2204,7 +2330,12 @@ class AggOp {
   AggTable t_;
   DevBuf d_slots_, d_special_, d_ng_, d_err_, d_mm_, d_frow_, d_fval_, d_fst_;
   DevBuf d_ckey_, d_cprio_, d_cval_, d_cn_, d_cskey_, d_csval_;
-  PinnedBuf pinned_meta_, pinned_emit_;
+  PinnedBuf pinned_meta_, pinned_nulls_;
+  // host emit state (emit_begin .. emit_end)
+  DevBuf d_emit_nulls_;
+  int emit_null_used_ = 0;
+  std::vector<DevBuf> emit_keep_;
+  int64_t emit_d2h_bytes_ = 0, emit_host_copy_bytes_ = 0;
   // two-phase scratch (allocated on first large chunk)
   bool agg2_p16_en_ = true;   // AURON_AGG2_P16=0 disables the adaptive path
   bool p16_decided_ = false;  // one key-range probe (chunk 1)
@@ -2859,6 +2990,7 @@ struct Runtime {
   std::vector<OutField> out_fields;
   int ipc_codec_ = 0;  // IpcReader block codec (SPARK_IO_COMPRESSION_CODEC)
   std::vector<std::pair<int64_t, std::vector<HostOutCol>>> outputs;
+  int64_t emit_d2h_bytes_ = 0;  // terminal Filter/Projection downloads
   size_t emit_idx = 0;
   // device-resident outputs (AURON_HIP_DEVICE_OUTPUT): exported through
   // import_device_batch; DevBufs stay owned here until finalize
@@ -3086,6 +3218,16 @@ struct Runtime {
       metrics["agg_update_rows"] = first_agg->update_rows_;
       metrics["spill_count"] = first_agg->spill_count_ + last_agg->spill_count_;
     }
+    // host-emit accounting: payload bytes copied down into export buffers,
+    // and payload bytes moved again by a host memcpy on the way out
+    int64_t d2h_bytes = emit_d2h_bytes_, host_copy_bytes = 0;
+    for (Stage& st : stages_)
+      if (st.kind == Stage::AggS) {
+        d2h_bytes += st.agg->emit_d2h_bytes_;
+        host_copy_bytes += st.agg->emit_host_copy_bytes_;
+      }
+    metrics["emit_d2h_bytes"] = d2h_bytes;
+    metrics["emit_host_copy_bytes"] = host_copy_bytes;
     metrics["input_rows"] = input_rows;
     int64_t out_rows = 0;
     for (auto& o : outputs) out_rows += o.first;
@@ -3177,39 +3319,46 @@ struct Runtime {
   }
 
   // terminal Filter/Projection output: download one device batch into the
-  // host output queue
+  // host output queue (export buffers filled by the D2H, one sync)
   void emit_host(DevBatch&& b) {
     const int64_t n = b.num_rows;
     if (n == 0) return;
     std::vector<HostOutCol> cols(b.cols.size());
+    DevBuf d_nulls(b.cols.size() * 4);
+    PinnedBuf h_nulls(b.cols.size() * 4);
+    AURON_HIP(hipMemsetAsync(d_nulls.get(), 0, b.cols.size() * 4, stream));
+    auto d2h = [&](HostBuf* dst, const void* dev, size_t len) {
+      dst->alloc(len);
+      if (len == 0) return;
+      AURON_HIP(hipMemcpyAsync(dst->data(), dev, len, hipMemcpyDeviceToHost,
+                               stream));
+      emit_d2h_bytes_ += (int64_t)len;
+    };
     for (size_t i = 0; i < b.cols.size(); i++) {
       const DevColumn& c = b.cols[i];
       HostOutCol& h = cols[i];
       h.dt = c.dt;
       if (c.dt == DType::Binary || c.dt == DType::Utf8) {
-        h.offsets.resize(n + 1);
-        AURON_HIP(hipMemcpyAsync(h.offsets.data(), c.offsets, (n + 1) * 4,
-                                 hipMemcpyDeviceToHost, stream));
-        h.values.resize((size_t)c.data_len);
-        if (c.data_len > 0)
-          AURON_HIP(hipMemcpyAsync(h.values.data(), c.values,
-                                   (size_t)c.data_len, hipMemcpyDeviceToHost,
-                                   stream));
+        d2h(&h.offsets, c.offsets, (size_t)(n + 1) * 4);
+        d2h(&h.values, c.values, (size_t)c.data_len);
       } else {
         const size_t w = dtype_width(c.dt);
         if (w == 0) FAIL("terminal output: unsupported column dtype");
-        h.values.resize((size_t)n * w);
-        AURON_HIP(hipMemcpyAsync(h.values.data(), c.values, (size_t)n * w,
-                                 hipMemcpyDeviceToHost, stream));
+        d2h(&h.values, c.values, (size_t)n * w);
       }
       if (c.validity) {
-        h.validity.resize((size_t)(n + 7) / 8);
-        AURON_HIP(hipMemcpyAsync(h.validity.data(), c.validity,
-                                 h.validity.size(), hipMemcpyDeviceToHost,
-                                 stream));
+        launch_bitmap_null_count(c.validity, n, d_nulls.get<uint32_t>() + i,
+                                 stream);
+        d2h(&h.validity, c.validity, (size_t)(n + 7) / 8);
       }
     }
+    AURON_HIP(hipMemcpyAsync(h_nulls.get(), d_nulls.get(), b.cols.size() * 4,
+                             hipMemcpyDeviceToHost, stream));
     AURON_HIP(hipStreamSynchronize(stream));
+    for (size_t i = 0; i < cols.size(); i++) {
+      cols[i].null_count = (int64_t)h_nulls.get<uint32_t>()[i];
+      if (cols[i].null_count == 0) cols[i].validity.free();
+    }
     outputs.emplace_back(n, std::move(cols));
   }
 
@@ -3222,9 +3371,12 @@ struct Runtime {
       const bool binary = h.dt == DType::Binary || h.dt == DType::Utf8;
       b.cols.push_back(upload_column(
           h.dt, ob.first, h.values.data(), h.values.size(),
-          binary ? h.offsets.data() : nullptr, h.validity.data(),
-          h.validity.size(), stream));
+          binary ? h.offs() : nullptr, h.validity.data(), h.validity.size(),
+          stream));
     }
+    // the sources are pinned, so the uploads are truly asynchronous: drain
+    // them before the caller lets the buffers go back to the pool
+    AURON_HIP(hipStreamSynchronize(stream));
     return b;
   }
 

@@ -151,7 +151,8 @@ void launch_agg_merge_spill(const AggTable& t, const int64_t* keys,
 // num_out (device). out_slot holds the source slot index per group.
 void launch_agg_compact(const AggTable& t, uint32_t* out_slot,
                         unsigned long long* out_first_row,
-                        unsigned long long* num_out, hipStream_t s);
+                        unsigned long long* num_out, int64_t max_out,
+                        hipStream_t s);
 
 // divide sums by counts for AVG output columns (avg final = sum/count)
 void launch_avg_div(const double* sums, const long long* cnts, int64_t n,
@@ -166,7 +167,7 @@ void launch_agg_gather_out(const AggTable& t, const uint32_t* order_slots,
                            uint8_t* out_sum_validity, long long* out_counts,
                            double* out_mins, uint8_t* out_min_validity,
                            double* out_maxs, uint8_t* out_max_validity,
-                           hipStream_t s);
+                           uint32_t* null_counts, hipStream_t s);
 
 // freeze ordered groups into the Binary agg-buf wire format (a8):
 // pass 1 computes per-group byte length, host scans, pass 2 writes bytes.
@@ -236,7 +237,11 @@ void launch_first_capture_frozen(const AggTable& t, const int64_t* keys,
 // gather one FIRST-family output column (which: 0 = FIRST, 1 = IGNORES_NULL)
 void launch_first_gather(const AggTable& t, const uint32_t* order_slots,
                          int64_t num_groups, int which, double* out_vals,
-                         uint8_t* out_validity, hipStream_t s);
+                         uint8_t* out_validity, uint32_t* null_count,
+                         hipStream_t s);
+// *null_count += unset bits among the first n of an existing bitmap
+void launch_bitmap_null_count(const uint8_t* bitmap, int64_t n,
+                              uint32_t* null_count, hipStream_t s);
 
 // rebuild `src` table into the (larger, initialized) `dst` table; each source
 // slot holds a distinct key so plain stores after the CAS claim are race-free.
@@ -294,9 +299,12 @@ static_assert(sizeof(PartRow) == 24, "PartRow must be 24 bytes");
 constexpr int AGG2_GRID_LOG2_MAX = 10;
 // per-BLOCK bucket histogram into the bucket-major counts matrix
 // [nbuck << grid_log2]; 1024-thread blocks, the scatter's row traversal
+// kminmax non-null: also fold the order-mapped (key ^ sign bit) min/max of
+// the normal keys into kminmax[0] / kminmax[1] (caller presets ~0 / 0)
 void launch_agg2_hist(const int64_t* keys, const uint8_t* key_valid, int64_t n,
                       int nbuck_log2, int grid_log2, uint32_t* counts_matrix,
-                      uint32_t* special_rows, hipStream_t s);
+                      uint32_t* special_rows, unsigned long long* kminmax,
+                      hipStream_t s);
 // exclusive scan over the flat counts matrix -> per-(block,bucket) bases
 void scan_counts_matrix(const uint32_t* counts, uint32_t* scanned, int64_t n,
                         void* temp, size_t* temp_bytes, hipStream_t s);
@@ -396,10 +404,11 @@ void launch_gkey_rebuild(const AggTable& dst, const GKeyTable& dg,
 void launch_gkey_out_fixed(const GKeyTable& g, const uint32_t* order_slots,
                            int64_t n, const uint8_t* dts, int ncols, int col,
                            uint8_t* values, uint8_t* valid_bitmap,
-                           hipStream_t s);
+                           uint32_t* null_count, hipStream_t s);
 void launch_gkey_out_lens(const GKeyTable& g, const uint32_t* order_slots,
                           int64_t n, const uint8_t* dts, int ncols, int col,
-                          uint32_t* lens, uint8_t* valid_bitmap, hipStream_t s);
+                          uint32_t* lens, uint8_t* valid_bitmap,
+                          uint32_t* null_count, hipStream_t s);
 void launch_gkey_out_bytes(const GKeyTable& g, const uint32_t* order_slots,
                            int64_t n, const uint8_t* dts, int ncols, int col,
                            const int32_t* out_offsets, uint8_t* out_data,
@@ -486,7 +495,7 @@ void launch_ma_freeze_write(const AggTable& t, const MaDesc& d,
 void launch_ma_gather_out(const MaDesc& d, const MaAcc& m, int agg,
                           const uint32_t* order_slots, int64_t n,
                           uint8_t* values, uint8_t* valid_bitmap,
-                          hipStream_t s);
+                          uint32_t* null_count, hipStream_t s);
 // growth: re-probe occupied src slots into dst, carrying the bank columns
 void launch_ma_rebuild(const AggTable& dst, const MaAcc& dm,
                        const AggTable& src, const MaAcc& sm, int naggs,
@@ -503,9 +512,6 @@ void launch_def_expand_validity(const void* runs, int nruns,
 // scatter into 64B-aligned per-(block,bucket) ranges + 4096-slot bucket agg
 void launch_agg3_line_sizes(const uint32_t* counts, int64_t n,
                             uint32_t* sizes, int rec, hipStream_t s);
-void launch_keys_minmax(const int64_t* keys, const uint8_t* key_valid,
-                        int64_t n, unsigned long long* kminmax,
-                        hipStream_t s);
 // rec = 24 (i64 key) or 16 (u32 key offset from key_base — rows whose key
 // falls outside [key_base, key_base+2^32) bypass to the leftover list)
 void launch_agg3_scatter(const int64_t* keys, const uint8_t* key_valid,
@@ -559,9 +565,11 @@ void launch_pq_pages_compact(const PqGpuPage* pages, int npages,
                              const uint32_t* page_dense,
                              uint8_t* dense_blob, hipStream_t s);
 
-// sort groups by first_row: rocprim radix sort pairs wrapper
+// sort groups by first_row: rocprim radix sort pairs wrapper; only key bits
+// [0, end_bit) are compared (every key must be < 2^end_bit)
 void sort_pairs_u64_u32(const unsigned long long* keys_in, const uint32_t* vals_in,
                         unsigned long long* keys_out, uint32_t* vals_out,
-                        int64_t n, void* temp, size_t* temp_bytes, hipStream_t s);
+                        int64_t n, void* temp, size_t* temp_bytes, hipStream_t s,
+                        int end_bit = 64);
 
 }  // namespace auron

@@ -146,8 +146,9 @@ void launch_pmod(const int32_t* hashes, int64_t n, int32_t P, uint32_t* part_ids
 // below; also correct standalone).
 __device__ __forceinline__ void agg_accum_row(const AggTable t, int64_t key,
                                               bool knull, double val,
-                                              bool vvalid, uint64_t row) {
-  int64_t a = agg_upsert_slot(t, key, knull);
+                                              bool vvalid, uint64_t row,
+                                              uint32_t* new_groups) {
+  int64_t a = agg_upsert_slot_counted(t, key, knull, new_groups);
   if (a < 0) return;  // table full: error_flag raised, host aborts
   AggSlot* sl = &t.slots[a];
   // skip the atomic when first_row is already <= row: a stale (L1) read can
@@ -189,6 +190,7 @@ __global__ void k_agg_update(const AggTable t, const int64_t* __restrict__ keys,
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t mask = t.cap - 1;
+  uint32_t new_groups = 0;
   int64_t i0 = tid;
   for (; i0 + (RPT - 1) * stride < n; i0 += RPT * stride) {
     int64_t key[RPT];
@@ -235,7 +237,7 @@ __global__ void k_agg_update(const AggTable t, const int64_t* __restrict__ keys,
           coll_append(t, key[k], false, row, val[k]);
       } else {
         agg_accum_row(t, knull[k] ? 0 : key[k], knull[k], val[k], vvalid[k],
-                      row);
+                      row, &new_groups);
       }
     }
   }
@@ -243,8 +245,9 @@ __global__ void k_agg_update(const AggTable t, const int64_t* __restrict__ keys,
     bool kn = key_valid && !bit_get_dev(key_valid, i);
     bool vv = !val_valid || bit_get_dev(val_valid, i);
     agg_accum_row(t, kn ? 0 : keys[i], kn, vals[i], vv,
-                  row_offset + (uint64_t)i);
+                  row_offset + (uint64_t)i, &new_groups);
   }
+  agg_publish_new_groups(t, new_groups);
 }
 
 __global__ void k_agg_merge_frozen(const AggTable t,
@@ -254,10 +257,12 @@ __global__ void k_agg_merge_frozen(const AggTable t,
                                    const int32_t* __restrict__ acc_offsets,
                                    int64_t n, uint64_t row_offset,
                                    uint32_t layout) {
+  uint32_t new_groups = 0;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * blockDim.x) {
     bool knull = key_valid && !bit_get_dev(key_valid, i);
-    int64_t a = agg_upsert_slot(t, knull ? 0 : keys[i], knull);
+    int64_t a = agg_upsert_slot_counted(t, knull ? 0 : keys[i], knull,
+                                        &new_groups);
     if (a < 0) continue;
     AggSlot* sl = &t.slots[a];
     uint64_t row = row_offset + (uint64_t)i;
@@ -282,6 +287,7 @@ __global__ void k_agg_merge_frozen(const AggTable t,
       }
     }
   }
+  agg_publish_new_groups(t, new_groups);
 }
 
 __global__ void k_agg_merge_spill(const AggTable t,
@@ -363,19 +369,71 @@ void launch_agg_merge_spill(const AggTable& t, const int64_t* keys,
   check_launch("k_agg_merge_spill");
 }
 
-__global__ void k_agg_compact(const AggTable t, uint32_t* __restrict__ out_slot,
-                              unsigned long long* __restrict__ out_first_row,
-                              unsigned long long* __restrict__ num_out) {
-  int64_t total = t.cap + 2;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    bool used = (i < t.cap) ? (t.slots[i].key != KEY_EMPTY)
-                            : (t.special_used[i - t.cap] != 0);
-    if (used) {
-      unsigned long long idx = atomicAdd(num_out, 1ull);
-      out_slot[idx] = (uint32_t)i;
-      out_first_row[idx] = t.slots[i].first_row;
+// Tiled block compaction of the used slots into (slot, first_row) pairs.
+// Each thread loads CPT_ITEMS slot keys up front (independent loads, each
+// instruction covering 64 consecutive slots per wave), the used flags are
+// ranked with one ballot per item and a per-wave count in LDS, and the block
+// reserves its output range with ONE atomic per tile. The order of the list
+// is free: the caller sorts it by the unique first_row. Stores are bounded
+// by max_out (the table's group count, which sizes the outputs).
+static constexpr int CPT_ITEMS = 8;
+static constexpr int CPT_TILE = BLOCK * CPT_ITEMS;
+
+__global__ __launch_bounds__(BLOCK) void k_agg_compact(
+    const AggTable t, uint32_t* __restrict__ out_slot,
+    unsigned long long* __restrict__ out_first_row,
+    unsigned long long* __restrict__ num_out, unsigned long long max_out) {
+  __shared__ uint32_t wave_cnt[BLOCK / 64];
+  __shared__ unsigned long long tile_base;
+  const int64_t total = t.cap + 2;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const unsigned long long lanes_below = (1ull << lane) - 1ull;
+  for (int64_t base = (int64_t)blockIdx.x * CPT_TILE; base < total;
+       base += (int64_t)gridDim.x * CPT_TILE) {
+    long long key[CPT_ITEMS];
+#pragma unroll
+    for (int k = 0; k < CPT_ITEMS; k++) {
+      int64_t i = base + k * BLOCK + threadIdx.x;
+      key[k] = KEY_EMPTY;
+      if (i < t.cap) key[k] = t.slots[i].key;
     }
+    uint32_t rank[CPT_ITEMS];
+    uint32_t used = 0, wave_total = 0;
+#pragma unroll
+    for (int k = 0; k < CPT_ITEMS; k++) {
+      int64_t i = base + k * BLOCK + threadIdx.x;
+      bool u = key[k] != KEY_EMPTY;
+      if (i >= t.cap && i < total) u = t.special_used[i - t.cap] != 0;
+      unsigned long long b = __ballot(u);
+      rank[k] = wave_total + (uint32_t)__popcll(b & lanes_below);
+      wave_total += (uint32_t)__popcll(b);
+      used |= (u ? 1u : 0u) << k;
+    }
+    if (lane == 0) wave_cnt[wave] = wave_total;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      uint32_t tile_total = 0;
+      for (int w = 0; w < BLOCK / 64; w++) tile_total += wave_cnt[w];
+      tile_base = tile_total ? atomicAdd(num_out, (unsigned long long)tile_total)
+                             : 0ull;
+    }
+    __syncthreads();
+    unsigned long long at = tile_base;
+    for (int w = 0; w < wave; w++) at += wave_cnt[w];
+    unsigned long long fr[CPT_ITEMS];
+#pragma unroll
+    for (int k = 0; k < CPT_ITEMS; k++)
+      if (used & (1u << k))
+        fr[k] = t.slots[base + k * BLOCK + threadIdx.x].first_row;
+#pragma unroll
+    for (int k = 0; k < CPT_ITEMS; k++) {
+      unsigned long long idx = at + rank[k];
+      if ((used & (1u << k)) && idx < max_out) {
+        out_slot[idx] = (uint32_t)(base + k * BLOCK + threadIdx.x);
+        out_first_row[idx] = fr[k];
+      }
+    }
+    __syncthreads();  // wave_cnt / tile_base are rewritten by the next tile
   }
 }
 
@@ -389,8 +447,11 @@ __global__ void k_agg_gather_out(const AggTable t,
                                  double* __restrict__ mins,
                                  uint8_t* __restrict__ min_validity,
                                  double* __restrict__ maxs,
-                                 uint8_t* __restrict__ max_validity) {
-  // one thread per output byte-group of 8 rows for validity bitmaps
+                                 uint8_t* __restrict__ max_validity,
+                                 uint32_t* __restrict__ null_counts) {
+  // one thread per output byte-group of 8 rows for validity bitmaps; their
+  // nulls are summed into null_counts[0..3] = {key, sum, min, max}
+  uint32_t kn = 0, sn = 0, mn = 0, xn = 0;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < num_groups;
        i += (int64_t)gridDim.x * blockDim.x) {
     uint32_t s = order_slots[i];
@@ -416,7 +477,17 @@ __global__ void k_agg_gather_out(const AggTable t,
       if (sum_validity) sum_validity[i >> 3] = sb;
       if (min_validity) min_validity[i >> 3] = mb;
       if (max_validity) max_validity[i >> 3] = xb;
+      kn += byte_nulls(kb, i, num_groups);
+      sn += byte_nulls(sb, i, num_groups);
+      mn += byte_nulls(mb, i, num_groups);
+      xn += byte_nulls(xb, i, num_groups);
     }
+  }
+  if (null_counts) {
+    if (key_validity) wave_add_u32(&null_counts[0], kn);
+    if (sum_validity) wave_add_u32(&null_counts[1], sn);
+    if (min_validity) wave_add_u32(&null_counts[2], mn);
+    if (max_validity) wave_add_u32(&null_counts[3], xn);
   }
 }
 
@@ -509,9 +580,12 @@ void launch_agg_merge_frozen(const AggTable& t, const int64_t* keys,
 }
 void launch_agg_compact(const AggTable& t, uint32_t* out_slot,
                         unsigned long long* out_first_row,
-                        unsigned long long* num_out, hipStream_t s) {
-  hipLaunchKernelGGL(k_agg_compact, dim3(grid_for(t.cap + 2)), dim3(BLOCK), 0, s,
-                     t, out_slot, out_first_row, num_out);
+                        unsigned long long* num_out, int64_t max_out,
+                        hipStream_t s) {
+  int64_t tiles = (t.cap + 2 + CPT_TILE - 1) / CPT_TILE;
+  hipLaunchKernelGGL(k_agg_compact, dim3(grid_for(tiles * BLOCK)), dim3(BLOCK),
+                     0, s, t, out_slot, out_first_row, num_out,
+                     (unsigned long long)max_out);
   check_launch("k_agg_compact");
 }
 void launch_agg_gather_out(const AggTable& t, const uint32_t* order_slots,
@@ -520,11 +594,12 @@ void launch_agg_gather_out(const AggTable& t, const uint32_t* order_slots,
                            uint8_t* out_sum_validity, long long* out_counts,
                            double* out_mins, uint8_t* out_min_validity,
                            double* out_maxs, uint8_t* out_max_validity,
-                           hipStream_t s) {
+                           uint32_t* null_counts, hipStream_t s) {
   hipLaunchKernelGGL(k_agg_gather_out, dim3(grid_for(num_groups)), dim3(BLOCK),
                      0, s, t, order_slots, num_groups, out_keys,
                      out_key_validity, out_sums, out_sum_validity, out_counts,
-                     out_mins, out_min_validity, out_maxs, out_max_validity);
+                     out_mins, out_min_validity, out_maxs, out_max_validity,
+                     null_counts);
   check_launch("k_agg_gather_out");
 }
 void launch_agg_freeze_len(const AggTable& t, const uint32_t* order_slots,
@@ -752,7 +827,9 @@ __global__ void k_first_gather(const AggTable t,
                                const uint32_t* __restrict__ order_slots,
                                int64_t num_groups, int which,
                                double* __restrict__ out_vals,
-                               uint8_t* __restrict__ out_validity) {
+                               uint8_t* __restrict__ out_validity,
+                               uint32_t* __restrict__ null_count) {
+  uint32_t nulls = 0;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
        i < num_groups; i += (int64_t)gridDim.x * blockDim.x) {
     uint32_t s = order_slots[i];
@@ -763,16 +840,42 @@ __global__ void k_first_gather(const AggTable t,
         if (t.f_st[2 * order_slots[i + j] + which] == 2)
           b |= (uint8_t)(1u << j);
       out_validity[i >> 3] = b;
+      nulls += byte_nulls(b, i, num_groups);
     }
   }
+  if (null_count) wave_add_u32(null_count, nulls);
+}
+
+// null count of an existing validity bitmap (pass-through columns, whose
+// bitmap no gather kernel of ours built)
+__global__ void k_bitmap_null_count(const uint8_t* __restrict__ bitmap,
+                                    int64_t n, uint32_t* __restrict__ null_count) {
+  uint32_t nulls = 0;
+  const int64_t nbytes = (n + 7) / 8;
+  for (int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; b < nbytes;
+       b += (int64_t)gridDim.x * blockDim.x) {
+    uint8_t v = bitmap[b];
+    if (b * 8 + 8 > n) v &= (uint8_t)((1u << (n - b * 8)) - 1u);
+    nulls += byte_nulls(v, b * 8, n);
+  }
+  wave_add_u32(null_count, nulls);
+}
+
+void launch_bitmap_null_count(const uint8_t* bitmap, int64_t n,
+                              uint32_t* null_count, hipStream_t s) {
+  if (n == 0) return;
+  hipLaunchKernelGGL(k_bitmap_null_count, dim3(grid_for((n + 7) / 8)),
+                     dim3(BLOCK), 0, s, bitmap, n, null_count);
+  check_launch("k_bitmap_null_count");
 }
 
 void launch_first_gather(const AggTable& t, const uint32_t* order_slots,
                          int64_t num_groups, int which, double* out_vals,
-                         uint8_t* out_validity, hipStream_t s) {
+                         uint8_t* out_validity, uint32_t* null_count,
+                         hipStream_t s) {
   hipLaunchKernelGGL(k_first_gather, dim3(grid_for(num_groups)), dim3(BLOCK),
                      0, s, t, order_slots, num_groups, which, out_vals,
-                     out_validity);
+                     out_validity, null_count);
   check_launch("k_first_gather");
 }
 
@@ -938,9 +1041,11 @@ void launch_agg_rebuild(const AggTable& dst, const AggTable& src, hipStream_t s)
 
 void sort_pairs_u64_u32(const unsigned long long* keys_in, const uint32_t* vals_in,
                         unsigned long long* keys_out, uint32_t* vals_out,
-                        int64_t n, void* temp, size_t* temp_bytes, hipStream_t s) {
+                        int64_t n, void* temp, size_t* temp_bytes, hipStream_t s,
+                        int end_bit) {
   hipError_t e = rocprim::radix_sort_pairs(temp, *temp_bytes, keys_in, keys_out,
-                                           vals_in, vals_out, (size_t)n, 0, 64, s);
+                                           vals_in, vals_out, (size_t)n, 0,
+                                           end_bit, s);
   if (e != hipSuccess) abort();
 }
 

@@ -44,17 +44,25 @@ __device__ __forceinline__ uint32_t bucket_of(int64_t key, int nbuck_log2) {
 // Launched at 1024 threads: 16 waves per block, and the scatter
 // (kernels_agg3.hip) walks rows with the SAME grid and block geometry.
 
+// MINMAX: also track the order-mapped (sign bit flipped) min/max of the
+// NORMAL keys and publish them with one atomicMin/atomicMax per wave into
+// kminmax[0..1]. The engine reads the pair after the first chunk's histogram
+// to pick the packed-16B record layout, so the decision costs no pass over
+// the keys of its own.
+template <bool MINMAX>
 __global__ __launch_bounds__(1024) void k_agg2_hist(
     const int64_t* __restrict__ keys,
                             const uint8_t* __restrict__ key_valid, int64_t n,
                             int nbuck_log2, int grid_log2,
                             uint32_t* __restrict__ counts_matrix,
-                            uint32_t* __restrict__ special_rows) {
+                            uint32_t* __restrict__ special_rows,
+                            unsigned long long* __restrict__ kminmax) {
   extern __shared__ uint32_t lds_hist[];
   const uint32_t nbuck = 1u << nbuck_log2;
   for (uint32_t b = threadIdx.x; b < nbuck; b += blockDim.x) lds_hist[b] = 0;
   __syncthreads();
   uint32_t special = 0;
+  unsigned long long kmin = ~0ull, kmax = 0ull;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * blockDim.x) {
     bool knull = key_valid && !bit_get_dev(key_valid, i);
@@ -63,7 +71,26 @@ __global__ __launch_bounds__(1024) void k_agg2_hist(
       special++;
       continue;
     }
+    if (MINMAX) {
+      unsigned long long m = (unsigned long long)k ^ 0x8000000000000000ull;
+      kmin = m < kmin ? m : kmin;
+      kmax = m > kmax ? m : kmax;
+    }
     atomicAdd(&lds_hist[bucket_of(k, nbuck_log2)], 1u);
+  }
+  if (MINMAX) {
+    // every lane takes part in the shuffles; lanes without a normal key
+    // carry the identities
+    for (int off = 32; off > 0; off >>= 1) {
+      unsigned long long omin = __shfl_xor(kmin, off);
+      unsigned long long omax = __shfl_xor(kmax, off);
+      kmin = omin < kmin ? omin : kmin;
+      kmax = omax > kmax ? omax : kmax;
+    }
+    if ((threadIdx.x & 63) == 0 && kmin != ~0ull) {
+      atomicMin(&kminmax[0], kmin);
+      atomicMax(&kminmax[1], kmax);
+    }
   }
   __syncthreads();
   for (uint32_t b = threadIdx.x; b < nbuck; b += blockDim.x)
@@ -103,9 +130,10 @@ __global__ void k_agg2_specials(const AggTable t,
 __global__ void k_agg2_merge_groups(const AggTable t,
                                     const StagedGroup* __restrict__ staged,
                                     int64_t n, uint64_t row_offset) {
+  uint32_t new_groups = 0;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * blockDim.x) {
-    int64_t a = agg_upsert_slot(t, staged[i].key, false);
+    int64_t a = agg_upsert_slot_counted(t, staged[i].key, false, &new_groups);
     if (a < 0) continue;  // probe exhausted: error bit 1 raised
     AggSlot* sl = &t.slots[a];
     unsigned long long cf = staged[i].cnt_first;
@@ -117,15 +145,17 @@ __global__ void k_agg2_merge_groups(const AggTable t,
       atomicAdd(&sl->cnt, (unsigned long long)cnt);
     }
   }
+  agg_publish_new_groups(t, new_groups);
 }
 
 // leftover raw rows (LDS window overflow — rare): single-phase accumulate
 __global__ void k_agg2_leftovers(const AggTable t,
                                  const PartRow* __restrict__ rows, int64_t n,
                                  uint64_t row_offset) {
+  uint32_t new_groups = 0;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * blockDim.x) {
-    int64_t a = agg_upsert_slot(t, rows[i].key, false);
+    int64_t a = agg_upsert_slot_counted(t, rows[i].key, false, &new_groups);
     if (a < 0) continue;  // probe exhausted: error bit 1 raised
     AggSlot* sl = &t.slots[a];
     uint32_t rv = rows[i].rowv;
@@ -136,6 +166,7 @@ __global__ void k_agg2_leftovers(const AggTable t,
       atomicAdd(&sl->cnt, 1ull);
     }
   }
+  agg_publish_new_groups(t, new_groups);
 }
 
 void launch_agg2_leftovers(const AggTable& t, const PartRow* rows, int64_t n,
@@ -147,11 +178,17 @@ void launch_agg2_leftovers(const AggTable& t, const PartRow* rows, int64_t n,
 
 void launch_agg2_hist(const int64_t* keys, const uint8_t* key_valid, int64_t n,
                       int nbuck_log2, int grid_log2, uint32_t* counts_matrix,
-                      uint32_t* special_rows, hipStream_t s) {
+                      uint32_t* special_rows, unsigned long long* kminmax,
+                      hipStream_t s) {
   size_t lds = (size_t)(1u << nbuck_log2) * 4;
-  hipLaunchKernelGGL(k_agg2_hist, dim3(1 << grid_log2), dim3(1024), lds, s,
-                     keys, key_valid, n, nbuck_log2, grid_log2, counts_matrix,
-                     special_rows);
+  if (kminmax)
+    hipLaunchKernelGGL(k_agg2_hist<true>, dim3(1 << grid_log2), dim3(1024),
+                       lds, s, keys, key_valid, n, nbuck_log2, grid_log2,
+                       counts_matrix, special_rows, kminmax);
+  else
+    hipLaunchKernelGGL(k_agg2_hist<false>, dim3(1 << grid_log2), dim3(1024),
+                       lds, s, keys, key_valid, n, nbuck_log2, grid_log2,
+                       counts_matrix, special_rows, kminmax);
   check_launch("k_agg2_hist");
 }
 

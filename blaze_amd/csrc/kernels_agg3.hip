@@ -75,38 +75,6 @@ static constexpr int A3_RETRY_BYPASS = 4;
 static constexpr int A3_RPT = 2;  // default; AURON_AGG2_RPT=4 selects the
                                   // wider tile instantiation
 
-// NORMAL-key min/max probe (order-mapped u64): lets the engine choose the
-// packed-16B record layout BEFORE the first chunk's scatter (the probe is
-// one 8 B/row read, ~0.35 ms per 256M rows — the 24B chunk it replaces
-// costs ~2.8 ms more than a packed one).
-__global__ void k_keys_minmax(const int64_t* __restrict__ keys,
-                              const uint8_t* __restrict__ key_valid,
-                              int64_t n,
-                              unsigned long long* __restrict__ kminmax) {
-  unsigned long long kmin = ~0ull, kmax = 0ull;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    if (key_valid && !bit_get_dev(key_valid, i)) continue;
-    int64_t k = keys[i];
-    if (k == KEY_EMPTY) continue;
-    unsigned long long m = (unsigned long long)k ^ 0x8000000000000000ull;
-    kmin = m < kmin ? m : kmin;
-    kmax = m > kmax ? m : kmax;
-  }
-  if (kmin != ~0ull) {
-    atomicMin(&kminmax[0], kmin);
-    atomicMax(&kminmax[1], kmax);
-  }
-}
-
-void launch_keys_minmax(const int64_t* keys, const uint8_t* key_valid,
-                        int64_t n, unsigned long long* kminmax,
-                        hipStream_t s) {
-  hipLaunchKernelGGL(k_keys_minmax, dim3(512), dim3(256), 0, s, keys,
-                     key_valid, n, kminmax);
-  check_launch("k_keys_minmax");
-}
-
 // REC = 24: [i64 key][f64 val][u32 rowv] (pad to 24). REC = 16: the key is
 // stored as a u32 OFFSET from key_base packed with rowv into one u64 —
 // [u64 koff|rowv<<32][f64 val] — 33% less scatter/bucket HBM traffic. Rows

@@ -390,8 +390,10 @@ __global__ void k_gkey_out_fixed(const GKeyTable g,
                                  int64_t n, const uint8_t* __restrict__ dts,
                                  int ncols, int col,
                                  uint8_t* __restrict__ values,
-                                 uint8_t* __restrict__ valid_bitmap) {
+                                 uint8_t* __restrict__ valid_bitmap,
+                                 uint32_t* __restrict__ null_count) {
   const int w = gk_col_width(dts[col]);
+  uint32_t nulls = 0;
   int64_t nbytes = (n + 7) / 8;
   for (int64_t byte = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
        byte < nbytes; byte += (int64_t)gridDim.x * blockDim.x) {
@@ -408,16 +410,18 @@ __global__ void k_gkey_out_fixed(const GKeyTable g,
       }
     }
     valid_bitmap[byte] = bm;
+    nulls += byte_nulls(bm, byte * 8, n);
   }
+  if (null_count) wave_add_u32(null_count, nulls);
 }
 
 void launch_gkey_out_fixed(const GKeyTable& g, const uint32_t* order_slots,
                            int64_t n, const uint8_t* dts, int ncols, int col,
                            uint8_t* values, uint8_t* valid_bitmap,
-                           hipStream_t s) {
+                           uint32_t* null_count, hipStream_t s) {
   hipLaunchKernelGGL(k_gkey_out_fixed, dim3(ggrid((n + 7) / 8)), dim3(GBLOCK),
                      0, s, g, order_slots, n, dts, ncols, col, values,
-                     valid_bitmap);
+                     valid_bitmap, null_count);
   check_launch("k_gkey_out_fixed");
 }
 
@@ -425,7 +429,9 @@ __global__ void k_gkey_out_lens(const GKeyTable g,
                                 const uint32_t* __restrict__ order_slots,
                                 int64_t n, const uint8_t* __restrict__ dts,
                                 int ncols, int col, uint32_t* __restrict__ lens,
-                                uint8_t* __restrict__ valid_bitmap) {
+                                uint8_t* __restrict__ valid_bitmap,
+                                uint32_t* __restrict__ null_count) {
+  uint32_t nulls = 0;
   int64_t nbytes = (n + 7) / 8;
   for (int64_t byte = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
        byte < nbytes; byte += (int64_t)gridDim.x * blockDim.x) {
@@ -442,16 +448,18 @@ __global__ void k_gkey_out_lens(const GKeyTable g,
       lens[i] = sl;
     }
     valid_bitmap[byte] = bm;
+    nulls += byte_nulls(bm, byte * 8, n);
   }
+  if (null_count) wave_add_u32(null_count, nulls);
 }
 
 void launch_gkey_out_lens(const GKeyTable& g, const uint32_t* order_slots,
                           int64_t n, const uint8_t* dts, int ncols, int col,
                           uint32_t* lens, uint8_t* valid_bitmap,
-                          hipStream_t s) {
+                          uint32_t* null_count, hipStream_t s) {
   hipLaunchKernelGGL(k_gkey_out_lens, dim3(ggrid((n + 7) / 8)), dim3(GBLOCK),
                      0, s, g, order_slots, n, dts, ncols, col, lens,
-                     valid_bitmap);
+                     valid_bitmap, null_count);
   check_launch("k_gkey_out_lens");
 }
 

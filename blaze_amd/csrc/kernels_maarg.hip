@@ -676,7 +676,9 @@ void launch_ma_first_capture_frozen(const AggTable& t, const MaDesc& d,
 __global__ void k_ma_gather_out(const MaDesc d, const MaAcc m, int agg,
                                 const uint32_t* __restrict__ order_slots,
                                 int64_t n, uint8_t* __restrict__ values,
-                                uint8_t* __restrict__ valid_bitmap) {
+                                uint8_t* __restrict__ valid_bitmap,
+                                uint32_t* __restrict__ null_count) {
+  uint32_t nulls = 0;
   const MaAgg& ag = d.a[agg];
   int w = ma_prim_w(ag);
   int64_t nbytes = (n + 7) / 8;
@@ -727,15 +729,18 @@ __global__ void k_ma_gather_out(const MaDesc d, const MaAcc m, int agg,
         values[i * ow + x] = valid ? (uint8_t)(bits >> (8 * x)) : 0;
     }
     valid_bitmap[byte] = bm;
+    nulls += byte_nulls(bm, byte * 8, n);
   }
+  if (null_count) wave_add_u32(null_count, nulls);
 }
 
 void launch_ma_gather_out(const MaDesc& d, const MaAcc& m, int agg,
                           const uint32_t* order_slots, int64_t n,
                           uint8_t* values, uint8_t* valid_bitmap,
-                          hipStream_t s) {
+                          uint32_t* null_count, hipStream_t s) {
   hipLaunchKernelGGL(k_ma_gather_out, dim3(mgrid((n + 7) / 8)), dim3(MBLOCK),
-                     0, s, d, m, agg, order_slots, n, values, valid_bitmap);
+                     0, s, d, m, agg, order_slots, n, values, valid_bitmap,
+                     null_count);
   check_launch("k_ma_gather_out");
 }
 
