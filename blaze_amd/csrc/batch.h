@@ -101,6 +101,42 @@ DevColumn upload_column(DType dt, int64_t rows, const void* values,
 void scan_mask_positions(const uint8_t* mask, int64_t n, uint32_t* positions,
                          DevBuf* tmp, hipStream_t stream);
 
+// Device lens -> offsets: offsets[0..n] = exclusive scan of lens[0..n), the
+// total in slot n. Both buffers have n+1 slots (slot n of lens is only read).
+// `tmp` is the caller's grow-only scan scratch, `pinned_total` a pinned
+// 4-byte landing slot. Returns the total after its one stream sync.
+int64_t scan_lens_offsets(const uint32_t* lens, int64_t n, uint32_t* offsets,
+                          DevBuf* tmp, uint32_t* pinned_total,
+                          hipStream_t stream);
+
+// The stable radix sorts of kernels.h (only key bits [0, end_bit) compared)
+// with the scratch-size query done here; `tmp` is grow-only and may be
+// reused across calls on one stream.
+void sort_pairs(const uint32_t* keys_in, const uint32_t* vals_in,
+                uint32_t* keys_out, uint32_t* vals_out, int64_t n, int end_bit,
+                DevBuf* tmp, hipStream_t stream);
+void sort_pairs(const unsigned long long* keys_in, const uint32_t* vals_in,
+                unsigned long long* keys_out, uint32_t* vals_out, int64_t n,
+                int end_bit, DevBuf* tmp, hipStream_t stream);
+
+// Variable-width output layout: device lens[n] (int32) -> host exclusive scan
+// -> the n+1 offsets in the caller's offs[], uploaded to d_offs (the caller
+// keeps offs alive until its next sync: it is the source of the upload).
+// Arrow offsets are int32, so a total past INT32_MAX fails instead of
+// wrapping.
+void lens_to_offsets_into(const void* d_lens, int64_t n, int32_t* offs,
+                          int32_t* d_offs, hipStream_t stream);
+std::vector<int32_t> lens_to_offsets(const void* d_lens, int64_t n,
+                                     int32_t* d_offs, hipStream_t stream);
+
+// Rows sel[0..m) of column c as an owned column (validity carried when c has
+// one); binary offsets are scanned on the host (lens_to_offsets), which
+// syncs the stream once. A non-null host_offsets receives that host copy of
+// the m+1 offsets. 4/8-byte primitives and Binary/Utf8 only.
+DevColumn gather_column(const DevColumn& c, const uint32_t* sel, int64_t m,
+                        hipStream_t stream,
+                        std::vector<int32_t>* host_offsets = nullptr);
+
 // ---------------------------------------------------------------- sources --
 // Each source pushes its batches into `sink` and returns the input row count.
 using BatchSink = std::function<void(DevBatch&&)>;

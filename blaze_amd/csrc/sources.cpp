@@ -1,6 +1,7 @@
 // sources.cpp — the batch sources behind the operator chain (batch.h): the
-// ParquetScanExec scan and the IpcReaderExec reader, with the host->device
-// column upload and the mask scan they share with engine.cpp.
+// ParquetScanExec scan and the IpcReaderExec reader, and the helpers of
+// batch.h that more than one file uses: column upload and gather, the
+// one-call scans and sorts.
 #include <algorithm>
 #include <atomic>
 #include <future>
@@ -46,6 +47,106 @@ void scan_mask_positions(const uint8_t* mask, int64_t n, uint32_t* positions,
   scan_mask_u8(mask, positions, n, nullptr, &tb, stream);
   if (tb > tmp->size()) tmp->alloc(tb);
   scan_mask_u8(mask, positions, n, tmp->get(), &tb, stream);
+}
+
+int64_t scan_lens_offsets(const uint32_t* lens, int64_t n, uint32_t* offsets,
+                          DevBuf* tmp, uint32_t* pinned_total,
+                          hipStream_t stream) {
+  size_t tb = 0;
+  scan_counts_matrix(lens, offsets, n + 1, nullptr, &tb, stream);
+  if (tb > tmp->size()) tmp->alloc(tb);
+  scan_counts_matrix(lens, offsets, n + 1, tmp->get(), &tb, stream);
+  AURON_HIP(hipMemcpyAsync(pinned_total, offsets + n, 4, hipMemcpyDeviceToHost,
+                           stream));
+  AURON_HIP(hipStreamSynchronize(stream));
+  return (int64_t)*pinned_total;
+}
+
+void sort_pairs(const uint32_t* keys_in, const uint32_t* vals_in,
+                uint32_t* keys_out, uint32_t* vals_out, int64_t n, int end_bit,
+                DevBuf* tmp, hipStream_t stream) {
+  size_t tb = 0;
+  sort_pairs_u32_u32(keys_in, vals_in, keys_out, vals_out, n, end_bit, nullptr,
+                     &tb, stream);
+  if (tb > tmp->size()) tmp->alloc(tb);
+  sort_pairs_u32_u32(keys_in, vals_in, keys_out, vals_out, n, end_bit,
+                     tmp->get(), &tb, stream);
+}
+
+void sort_pairs(const unsigned long long* keys_in, const uint32_t* vals_in,
+                unsigned long long* keys_out, uint32_t* vals_out, int64_t n,
+                int end_bit, DevBuf* tmp, hipStream_t stream) {
+  size_t tb = 0;
+  sort_pairs_u64_u32(keys_in, vals_in, keys_out, vals_out, n, nullptr, &tb,
+                     stream, end_bit);
+  if (tb > tmp->size()) tmp->alloc(tb);
+  sort_pairs_u64_u32(keys_in, vals_in, keys_out, vals_out, n, tmp->get(), &tb,
+                     stream, end_bit);
+}
+
+void lens_to_offsets_into(const void* d_lens, int64_t n, int32_t* offs,
+                          int32_t* d_offs, hipStream_t stream) {
+  offs[0] = 0;
+  AURON_HIP(hipMemcpyAsync(offs + 1, d_lens, n * 4, hipMemcpyDeviceToHost,
+                           stream));
+  AURON_HIP(hipStreamSynchronize(stream));
+  int64_t total = 0;
+  for (int64_t i = 0; i < n; i++) {
+    total += offs[i + 1];
+    if (total > INT32_MAX)
+      FAIL("variable-width output exceeds 2 GiB in one batch (int32 offsets)");
+    offs[i + 1] = (int32_t)total;
+  }
+  AURON_HIP(hipMemcpyAsync(d_offs, offs, (n + 1) * 4, hipMemcpyHostToDevice,
+                           stream));
+}
+
+std::vector<int32_t> lens_to_offsets(const void* d_lens, int64_t n,
+                                     int32_t* d_offs, hipStream_t stream) {
+  std::vector<int32_t> offs(n + 1, 0);
+  lens_to_offsets_into(d_lens, n, offs.data(), d_offs, stream);
+  return offs;
+}
+
+DevColumn gather_column(const DevColumn& c, const uint32_t* sel, int64_t m,
+                        hipStream_t stream,
+                        std::vector<int32_t>* host_offsets) {
+  DevColumn out;
+  out.dt = c.dt;
+  out.len = m;
+  size_t w = dtype_width(c.dt);
+  if (c.dt == DType::Binary || c.dt == DType::Utf8) {
+    DevBuf lens(m * 4);
+    launch_gather_lens(c.offsets, sel, m, lens.get<int32_t>(), stream);
+    out.own_offsets.alloc((m + 1) * 4);
+    std::vector<int32_t> h_offs = lens_to_offsets(
+        lens.get(), m, out.own_offsets.get<int32_t>(), stream);
+    out.offsets = out.own_offsets.get<int32_t>();
+    out.data_len = h_offs[m];
+    out.own_values.alloc(out.data_len ? out.data_len : 1);
+    launch_gather_bytes((const uint8_t*)c.values, c.offsets, sel,
+                        out.own_offsets.get<int32_t>(), m,
+                        out.own_values.get<uint8_t>(), stream);
+    if (host_offsets) *host_offsets = std::move(h_offs);
+  } else if (w == 8) {
+    out.own_values.alloc(m * 8);
+    launch_gather_8((const uint8_t*)c.values, sel, m,
+                    out.own_values.get<uint8_t>(), stream);
+  } else if (w == 4) {
+    out.own_values.alloc(m * 4);
+    launch_gather_4((const uint8_t*)c.values, sel, m,
+                    out.own_values.get<uint8_t>(), stream);
+  } else {
+    FAIL("column gather supports Binary/Utf8 and 4/8-byte primitives");
+  }
+  out.values = out.own_values.get();
+  if (c.validity) {
+    out.own_validity.alloc((m + 7) / 8);
+    launch_gather_bits(c.validity, sel, m, out.own_validity.get<uint8_t>(),
+                       stream);
+    out.validity = out.own_validity.get<uint8_t>();
+  }
+  return out;
 }
 
 namespace {

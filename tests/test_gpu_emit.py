@@ -283,3 +283,118 @@ def test_emit_table_smaller_than_a_compaction_tile(budget, groups, exported):
             assert nc[col] == (0 if v is None else int((~v).sum()))
             assert v is None or nc[col] > 0
         assert nc[2] == 0
+
+
+# ---- terminal Filter: the Runtime's own host emit ---------------------------
+
+def _utf8(strings):
+    raw = [s.encode() for s in strings]
+    offs = np.zeros(len(raw) + 1, dtype=np.int32)
+    offs[1:] = np.cumsum([len(r) for r in raw])
+    return np.frombuffer(b"".join(raw), dtype=np.uint8).copy(), offs
+
+
+def _filter_task():
+    """Filter(b IS NOT NULL) as the plan's last stage over (a Int64, b Int32,
+    s Utf8), all nullable."""
+    reader = plan.ffi_reader([plan.field("a", plan.DT_INT64, True),
+                              plan.field("b", plan.DT_INT32, True),
+                              plan.field("s", plan.DT_UTF8, True)], "input0")
+    return plan.task_definition(
+        plan.filter_node(reader, [plan.is_not_null(plan.column("b", 1))]))
+
+
+def _filter_input(m, splits):
+    """Input batches of the given sizes in which exactly m rows pass. b is
+    null on the dropped rows only, so its gathered bitmap has no zero bit; a
+    and s carry nulls among the passing rows (s: empty strings too). With
+    m == 1 the one passing row has a null a and a valid s."""
+    n = sum(splits)
+    rng = np.random.default_rng(4000 + m)
+    sel = np.zeros(n, bool)
+    sel[rng.permutation(n)[:m]] = True
+    a = rng.integers(-1000, 1000, n).astype(np.int64)
+    av = rng.random(n) >= 0.3
+    b = rng.integers(-1000, 1000, n).astype(np.int32)
+    vocab = ["", "x", "天地人", "row_0123456789"]
+    strs = [vocab[i] for i in rng.integers(0, len(vocab), n)]
+    sv = rng.random(n) >= 0.3
+    if m == 1:
+        av[sel], sv[sel] = False, True
+    batches, parts, at = [], [], 0
+    for k in splits:
+        r = slice(at, at + k)
+        data, offs = _utf8(strs[r])
+        batches.append([(a[r], av[r]), (b[r], sel[r]),
+                        ("binary", data, offs, sv[r])])
+        parts.append(dict(sel=sel[r], a=a[r], av=av[r], b=b[r],
+                          strs=strs[at:at + k], sv=sv[r]))
+        at += k
+    return batches, [p for p in parts if p["sel"].any()]
+
+
+FILTER_CASES = [(1, [3]), (9, [20]), (1001, [130, 1500, 63])]
+
+
+def _run_filter(m, splits):
+    batches, parts = _filter_input(m, splits)
+    assert sum(int(p["sel"].sum()) for p in parts) == m
+    # every input batch has a dropped row, so b always arrives with a bitmap
+    assert all(not p["sel"].all() for p in parts)
+    t = blaze_amd.Task(_filter_task(), batches=batches)
+    outs = t.run()
+    metrics = (t.metric("emit_d2h_bytes"), t.metric("emit_host_copy_bytes"))
+    t.finalize()
+    return outs, parts, metrics
+
+
+@pytest.mark.parametrize("m,splits", FILTER_CASES)
+def test_terminal_filter_null_counts_and_bitmaps(m, splits, exported):
+    """One output batch per input batch with a passing row; bitmaps of 1, 9
+    and (over three unequal batches) 1 001 rows in all end mid-byte. Per
+    batch: values, offsets and validity exact, the exported null_count of
+    each child is the number of nulls among the selected rows, and a column
+    whose selected rows have no nulls comes back without a bitmap."""
+    outs, parts, _ = _run_filter(m, splits)
+    assert len(outs) == len(parts) == len(exported)
+    for o, p, nc in zip(outs, parts, exported):
+        sel = p["sel"]
+        k = int(sel.sum())
+        want_valid = [p["av"][sel], np.ones(k, bool), p["sv"][sel]]
+        for col in range(3):
+            nulls = int((~want_valid[col]).sum())
+            assert nc[col] == nulls
+            if nulls == 0:
+                assert o[col]["valid"] is None
+            else:
+                np.testing.assert_array_equal(o[col]["valid"],
+                                              want_valid[col])
+        assert o[1]["valid"] is None        # b: bitmap without a zero bit
+        np.testing.assert_array_equal(o[0]["values"], p["a"][sel])
+        assert o[1]["values"].dtype == np.int32
+        np.testing.assert_array_equal(o[1]["values"], p["b"][sel])
+        data, offs = _utf8([p["strs"][i] for i in np.flatnonzero(sel)])
+        np.testing.assert_array_equal(o[2]["offsets"], offs)
+        np.testing.assert_array_equal(o[2]["data"], data)
+    if m == 1:
+        assert exported[0] == [1, 0, 0]
+
+
+@pytest.mark.parametrize("m,splits", FILTER_CASES)
+def test_terminal_filter_byte_metric(m, splits):
+    """Payload only: values, (k+1)*4 offsets and the data bytes of the Utf8
+    column, and (k+7)//8 for every column that arrived with a bitmap. The
+    gather carries an input bitmap along and the download happens before the
+    null count is known, so b's all-ones bitmap counts. The input side drops
+    the bitmap of a column without nulls in that batch."""
+    outs, parts, (d2h, host_copy) = _run_filter(m, splits)
+    want = 0
+    for p in parts:
+        sel = p["sel"]
+        k = int(sel.sum())
+        data, _ = _utf8([p["strs"][i] for i in np.flatnonzero(sel)])
+        want += k * 8 + k * 4 + (k + 1) * 4 + len(data)
+        carried = [not p["av"].all(), True, not p["sv"].all()]
+        want += sum(carried) * ((k + 7) // 8)
+    assert host_copy == 0
+    assert d2h == want
